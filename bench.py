@@ -37,6 +37,9 @@ before the timed region; synthetic data (the reference's own initial guess, Newt
 Prints ONE JSON line (rank 0).  `roofline` is for the kernel with the largest share of the timed region,
 measured with HIP events on the library's stream (bk_prof_*); `cpu_baseline` times the NumPy/SciPy oracle
 (reference formulation: assembled sparse L1, MGS2 GMRES) on a bounded sample on this host.
+
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float64; the state as a fixed, seeded
+sample of at most DUMP_STATE_MAX values), so that two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -53,6 +56,7 @@ if ROOT not in sys.path:
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s measured achievable
+DUMP_STATE_MAX = 1 << 22       # --dump-outputs: values of the state written at most (fp64: 32 MiB)
 
 
 def parse():
@@ -94,6 +98,10 @@ def parse():
     ap.add_argument("--linsolver", default="gmres", choices=["gmres", "minres"],
                     help="gmres: GMRESKrylovKit(30), the reference example's solver (the headline workload); minres: "
                          "KrylovLS(KrylovAlg = :minres), valid because the SH Jacobian is symmetric (experiment)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; a state "
+                         f"longer than {DUMP_STATE_MAX} values as a fixed seeded sample of that many) so that two builds can be "
+                         "compared output for output")
     return ap.parse_args()
 
 
@@ -254,6 +262,43 @@ def thread_counts():
     n = available_cpus()
     cand = sorted({min(n, c) for c in (8, 16, 32, 64, n)})
     return cand
+
+
+def state_sample(vec, prob, world):
+    """The values of a (z-slab distributed) state that --dump-outputs writes, in global index order, on every rank: all of
+    them up to DUMP_STATE_MAX, else one seeded random index in each of DUMP_STATE_MAX equal strata -- the same indices for
+    every run and every build on the same grid."""
+    import numpy as np
+    import torch
+    n = prob.nglobal
+    if n <= DUMP_STATE_MAX:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        stride = n // DUMP_STATE_MAX
+        idx = np.arange(DUMP_STATE_MAX, dtype=np.int64) * stride + np.random.default_rng(0).integers(0, stride, DUMP_STATE_MAX)
+    off = prob.slab[0] * int(np.prod(prob.dims[:-1])) if world > 1 else 0
+    mine = idx[(idx >= off) & (idx < off + prob.nlocal)] - off
+    assert vec.t.numel() == prob.nlocal, (vec.t.numel(), prob.nlocal)      # every index in bounds before it reaches the device
+    vals = vec.t[torch.from_numpy(mine).to(vec.t.device)].cpu().numpy()
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, (off, vals))
+        vals = np.concatenate([v for _, v in sorted(parts, key=lambda ov: ov[0])])
+    assert vals.size == idx.size, (vals.size, idx.size)
+    return vals
+
+
+def dump_outputs(d, arrays):
+    """Write each array as d/<name>.npy in float64; returns {name: shape}."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    shapes = {}
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        np.save(os.path.join(d, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def self_launch(args):
@@ -432,6 +477,16 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if hostcomm_mode else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+
+    # ---- --dump-outputs: what the last timed step returned (newton_palc_native: corrected state and parameter, residual history,
+    # counts); its inputs are the same in every run with the same arguments
+    dumped = None
+    if args.dump_outputs:
+        u_s = state_sample(last["u"].u, prob, world)
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, {
+                "u": u_s, "p": [last["u"].p], "residuals": last["residuals"], "itnewton": [last["itnewton"]],
+                "itlinear": [last["itlineartot"]], "converged": [float(last["converged"])]})
 
     # ---- fixed input (VERDICT r5 Next 7): the SAME step from the committed cell solutions tests/golden/bench_cell_states.npz
     # (CPU oracle, generated once: scripts/gen_bench_cell_states.py) -- its operator-application count does not depend on the last
@@ -694,6 +749,11 @@ def main():
             except Exception as e:  # the baseline must not take the bench line down
                 cb = {"value": None, "unit": "steps/s", "cores": 1, "kind": "port", "sample": f"failed: {e!r}"}
         out["cpu_baseline"] = cb
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped,
+                                   "u": "all values" if prob.nglobal <= DUMP_STATE_MAX else
+                                        f"{DUMP_STATE_MAX} of {prob.nglobal} values: one index per stratum of {prob.nglobal // DUMP_STATE_MAX}, "
+                                        "numpy default_rng(0)"}
         FINAL_LINE.append(json.dumps(out))
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -741,6 +801,15 @@ def run_branch_workload(args, ctx, hip, Cn, prob, P, ls, u0, branch_setup, barri
     nst = len(br.param) - 1
     t_init = init.get("seconds", 0.0)                         # two Newton solves + the eigensolve at the first point
     t_steps = sum(p_["seconds"] for p_ in per)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what continuation_native returned: the branch record (one entry per point, the last step's point last) and the
+        # eigenvalues and corrector residuals of the last point (the state itself is not part of the record: save_sol = False)
+        import numpy as np
+        ev = br.eig[-1] if br.eig and br.eig[-1] is not None else np.zeros(0, dtype=complex)
+        dumped = dump_outputs(args.dump_outputs, {
+            "param": br.param, "ds": br.ds, "itnewton": br.itnewton, "itlinear": br.itlinear, "n_unstable": br.n_unstable,
+            "n_imag": br.n_imag, "eig_re": np.real(ev), "eig_im": np.imag(ev), "residuals": br.residuals[-1]})
     if rank == 0:
         FINAL_LINE.append(json.dumps({
             "metric": "palc_continuation_steps_per_s", "value": nst / max(t_steps, 1e-9), "unit": "steps/s", "n_gpus": world,
@@ -757,7 +826,8 @@ def run_branch_workload(args, ctx, hip, Cn, prob, P, ls, u0, branch_setup, barri
                                              "see it: per_step[].eig_converged); 1e-8 is the tolerance it reaches within 20 restarts"),
                        "all_eigensolves_converged": all(p_["eig_converged"] for p_ in per) and bool(init.get("eig_converged", True)),
                        "initialisation": init, "setup_seconds": t_setup},
-            "per_step": per, "param": br.param, "n_unstable": br.n_unstable}))
+            "per_step": per, "param": br.param, "n_unstable": br.n_unstable,
+            **({"dump_outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {})}))
 
 
 # The ONE JSON line is the last thing this process writes: communicator / context teardown first (RCCL and the runtime
