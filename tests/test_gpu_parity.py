@@ -648,7 +648,7 @@ def test_symmetric_krylov_solvers_match_oracle(ctx):
         hip.MatrixFreeBLS(mn)(J, prob.vec(dR), prob.vec(dzu), 0.4, prob.vec(R), 0.3, dotscale=1.0 / n)
 
 
-@pytest.mark.parametrize("dims", [(64, 64, 64), (70, 34, 20), (128, 64, 32), (128, 64)])
+@pytest.mark.parametrize("dims", [(64, 64, 64), (70, 34, 20), (128, 64, 32), (128, 64), (256, 128, 128)])
 def test_fused_minres_passes_reproduce_the_separate_ones(ctx, dims):
     """Option minres_fused (default on): the Lanczos step's axpy + dot ride in the stencil kernel's store stage and
     r . M^-1 r comes out of the preconditioner's spectrum (Parseval) -- same iterates as with the separate passes (counts,
@@ -695,7 +695,7 @@ def test_fused_minres_passes_reproduce_the_separate_ones(ctx, dims):
         assert oko and abs(it1 - ito) <= max(2, ito // 4) and np.abs(x1 - xo).max() <= 1e-6 * np.abs(xo).max()
 
 
-@pytest.mark.parametrize("dims", [(64, 64, 64), (128, 64), (70, 34, 20)])
+@pytest.mark.parametrize("dims", [(64, 64, 64), (128, 64), (70, 34, 20), (256, 128, 128)])
 def test_minres_pair_update_is_bitwise_the_single_updates(ctx, dims):
     """Round 6 (option minres_pair_update, default on; csrc/solver.hip: minres_core, csrc/vecops.hip: v_minres_update2): the MINRES
     direction / solution update taken two iterations at a time -- 8 array streams instead of 2 x 6 -- performs the arithmetic of the
