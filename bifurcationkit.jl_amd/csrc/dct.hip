@@ -528,6 +528,43 @@ int dct_apply(bk_ctx* ctx, DctPlan* p, const double* v, double* out, int* dot_bl
     return 0;
 }
 
+// The applications x_{i+1} = cx_i x_i + ct Pl \ (d .* x_i), i < s, of bk_precond::apply_pw_chain on a single-rank plan whose passes all
+// run on the LDS FFT kernels with the round trip: the pass sequence of s dct_apply calls with their fused pointwise work, except that
+// each x-inverse pass but the last is the x turnaround (DctFuse::xfwd), which also runs the next application's x-forward pass on the
+// values it stores -- the same kernels' arithmetic, one read of x_{i+1} and one launch fewer per link.  The spectrum X_i always sits
+// in t1 and the y-inverse output Y_i in t2 (an odd number of passes in between); nothing is allocated.
+static int dct_apply_pw_chain(bk_ctx* ctx, DctPlan* p, const double* x, const DctFuse& d, int s, const double* cx, double ct,
+                              double* const* outs) {
+    const int n0 = p->n[0], n1 = p->n[1], n2 = p->n[2], last = p->ndim - 1;
+    auto pass = [&](int a, int inverse, const double* in, double* o, int fuse, const DctFuse* f, double bytes) -> int {
+        ProfScope ps(ctx, "dct_pass", bytes * p->total);
+        return dct_axis_fft(ctx, n0, n1, n2, a, inverse, p->twid[a], in, o, p->lam[0], p->lam[1], p->ndim == 3 ? p->lam[2] : nullptr,
+                            p->shift, fuse, nullptr, nullptr, f);
+    };
+    DctFuse f0;
+    f0.u = d.u; f0.A = d.A; f0.B = d.B; f0.C = d.C;
+    BK_TRY(pass(0, 0, x, p->t1, 0, &f0, 24.0));                       // X_0 = x-forward(d .* x)
+    for (int i = 0; i < s; ++i) {
+        double* bufs[2] = {p->t1, p->t2};
+        const double* src = p->t1;
+        int cur = 1;
+        for (int a = 1; a < last; ++a) { BK_TRY(pass(a, 0, src, bufs[cur], 0, nullptr, 16.0)); src = bufs[cur]; cur ^= 1; }
+        BK_TRY(pass(last, 0, src, bufs[cur], 2, nullptr, 16.0)); src = bufs[cur]; cur ^= 1;
+        for (int a = last - 1; a >= 1; --a) { BK_TRY(pass(a, 1, src, bufs[cur], 0, nullptr, 16.0)); src = bufs[cur]; cur ^= 1; }
+        DctFuse f = f0;
+        const bool shifted = cx[i] != 0.0;
+        if (shifted) { f.xadd = i == 0 ? x : outs[i - 1]; f.cx = cx[i]; f.ct = ct; }
+        if (i + 1 < s) {
+            // x_{i+1} = x-inverse(Y_i) [+ cx x_i] stored, and X_{i+1} = x-forward(d .* x_{i+1}) into t1: reads Y_i (+ x_i) and u, writes both
+            f.xfwd = p->t1;
+            BK_TRY(pass(0, 1, src, outs[i], 0, &f, shifted ? 40.0 : 32.0));
+        } else {
+            BK_TRY(pass(0, 1, src, outs[i], 0, shifted ? &f : nullptr, shifted ? 24.0 : 16.0));
+        }
+    }
+    return 0;
+}
+
 static int slab_tables_create(bk_ctx* ctx, DctPlan* p, int nl, bool even, double az);
 
 int dct_plan_create_dist(bk_ctx* ctx, const int n[3], const double ainv[3], double shift, int zlo, int zhi, DctPlan** out) {
@@ -818,6 +855,17 @@ struct ShDctPrecond : bk_precond {
         if (cx != 0.0) { f.xadd = x; f.cx = cx; f.ct = ct; }
         BK_TRY(plan->dist ? dct_apply_dist(ctx, plan, x, out, &f) : dct_apply(ctx, plan, x, out, nullptr, &f));
         return scale_after ? v_scale(ctx, n, ct, out) : 0;
+    }
+    int apply_pw_chain(const double* x, const DctFuse& d, int s, const double* cx, double ct, double* const* outs) override {
+        // single rank, neither distributed nor the slab emulation, every pass on the LDS FFT kernels with the round trip, every link
+        // fused as apply_pw would fuse it (a link without the x term stores the plain result: ct == 1); else the links one by one
+        bool ok = s >= 2 && plan->kind == 0 && !plan->dist && !plan->slab_ok && ctx->nranks == 1 && plan->ndim >= 2 &&
+                  ctx->opt("dct_fuse_pw", 1.0) != 0.0 && ctx->opt("dct_roundtrip", 1.0) != 0.0;
+        for (int a = 0; ok && a < plan->ndim; ++a) ok = plan->twid[a] != nullptr;
+        for (int i = 0; ok && i < s; ++i)
+            ok = (cx[i] != 0.0 || ct == 1.0) && pw_fused_ok(i == 0 ? x : outs[i - 1], d.u, outs[i]) && outs[i] != (i == 0 ? x : outs[i - 1]);
+        if (!ok) return bk_precond::apply_pw_chain(x, d, s, cx, ct, outs);
+        return dct_apply_pw_chain(ctx, plan, x, d, s, cx, ct, outs);
     }
     int apply_dot_pre_axpy(double* y, double c, const double* r, double* out, double* dot) override {
         // (plan->slab_ok: the cost model's slab emulation routes through dct_apply_slab, which only knows the stencil-free operator's fusions)

@@ -59,6 +59,10 @@ struct FftK {
     const double* fz_v;
     double fzA, fzB, fzC, fz_cx, fz_ct;
     double* fz_store;         // FZS (forward): the sample + fz_cx * fz_v[same index] is what gets transformed, and it is stored here
+    // TURN (x inverse, then the next x forward in the same tile residency): the stored inverse result, multiplied by
+    // fzA + u (fzB + fzC u) with u = turn_u[same index], is transformed forward and the spectrum is stored to turn_out
+    const double* turn_u;
+    double* turn_out;
     // SLAB kernels (z passes of the slab z-solve as forward / inverse HALVES, dct.hip: dct_apply_slab): the forward half stores
     // y^_k = sym_k f^_k and, from sums over the spectrum with the local basis phi, the values of y = B^-1 f at the four planes next to
     // the slab faces (planes 0, 1, nl-2, nl-1); the inverse half adds sym_k * sum_p phi_k(p) delta_p(line) -- the Woodbury correction,
@@ -381,9 +385,15 @@ __device__ __forceinline__ c2 lane_xor1(c2 v) { c2 r; r.x = lane_xor1(v.x); r.y 
 // FZS (round 6, with FZ, MODE 0): the second stream is ADDED -- sample + fz_cx * fz_v -- instead of entering a pointwise factor, and the
 // sum is stored to fz_store (the MINRES recurrence's y <- y + c r riding in the preconditioner's first pass: DctFuse::add).  A separate
 // instantiation: the kernels of the corrector's hot path are compiled exactly as before.
-template <int NT, int MODE, bool AX0, bool NTM, bool DOT = false, bool FZ = false, int SLAB = 0, bool FZS = false>   // MODE 0: forward, 1: inverse, 2: forward - symbol - inverse (AX0: 0 / 1 only)
+// TURN (with MODE 1, AX0): the x turnaround of a chain of stencil-free operator applications (dct.hip: dct_apply_pw_chain).  The
+// tile runs the MODE-1 inverse and stores p_{i+1} exactly as MODE 1 does (FZ: the shifted store ct * result + cx * p_i); a lane's
+// last-stage outputs are the samples its first-stage item of the forward pass takes in (fused_last2 / fused_first2 walk the same
+// (pair, group) map), so they stay in registers, are multiplied by the MODE-0 FZ factor of u and run the forward transform in the same
+// residency: one read of Y (+ p_i) and u, one write of p_{i+1} and X_{i+1}, instead of two passes.
+template <int NT, int MODE, bool AX0, bool NTM, bool DOT = false, bool FZ = false, int SLAB = 0, bool FZS = false, bool TURN = false>   // MODE 0: forward, 1: inverse, 2: forward - symbol - inverse (AX0: 0 / 1 only)
 __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P) {
     constexpr bool SPLIT = NT == 512;
+    static_assert(!TURN || (MODE == 1 && AX0 && !DOT && SLAB == 0 && !FZS && !SPLIT), "TURN: the x inverse pass only");
     static_assert(!FZS || (FZ && MODE == 0), "FZS: the x-forward pass only");
     static_assert(!SPLIT || (MODE == 2 && !AX0 && !FZ && SLAB == 0), "512 lanes: the z / y round trip only");
     static_assert(!FZ || (AX0 && MODE != 2), "FZ: x passes only");
@@ -471,6 +481,7 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
     // pfb; (axis >= 1) the 8 samples of item tid in pfa and of item tid + NT in pfb
     c2 pfa[8], pfb[SPLIT ? 1 : 8];
     c2 qfa[FZ ? 8 : 1], qfb[FZ ? 8 : 1];     // FZ: the second stream's values at the same indices (u forward, x inverse)
+    c2 ufa[TURN ? 8 : 1], ufb[TURN ? 8 : 1]; // TURN: u at the same indices (the forward half's factor)
     c2 dl[SLAB == 2 ? 4 : 1];                // SLAB 2: the correction's right-hand side at the four face planes, lines a / b of this item
     // (the host launches this kernel only when nfirst <= NT (AX0) / 2 NT, so the two register sets cover the tile)
     const bool act0 = tid < nfirst, act1 = !AX0 && !SPLIT && tid + NT < nfirst;
@@ -598,7 +609,8 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
             dl[I2].x = -ht * (a_ * nut_u.x); dl[I2].y = -ht * (a_ * nut_u.y);
             dl[I3].x = -ht * ((ca - a_) * nut_u.x + nut_w.x); dl[I3].y = -ht * ((cb - a_) * nut_u.y + nut_w.y);
         }
-        if (MODE != 1) {
+        // first stage from the sample registers, then the forward middle stages (MODE 0 / 2 here; TURN: after the inverse below)
+        auto front = [&]() {
             if (AX0) {
                 if (act0)
                     dctc::fused_first2(z + (size_t)(tid >> hbits) * pstride, N, bits, tid & ((1 << hbits) - 1),
@@ -613,10 +625,12 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                                                double* srow = P.fz_store + tile_base(tile) + (size_t)(2 * (tid >> hbits)) * lstride;
                                                st16(srow + 2 * j, ea, oa);
                                                st16(srow + lstride + 2 * j, eb, ob);
-                                           } else if (FZ) {
-                                               const int t = FZ ? s : 0;
+                                           } else if (FZ || TURN) {
+                                               const int t = (FZ || TURN) ? s : 0;
+                                               const c2 wa = TURN ? ufa[TURN ? t : 0] : qfa[FZ ? t : 0];
+                                               const c2 wb = TURN ? ufb[TURN ? t : 0] : qfb[FZ ? t : 0];
                                                auto d = [&](double u) { return P.fzA + u * (P.fzB + P.fzC * u); };
-                                               ea *= d(qfa[t].x); oa *= d(qfa[t].y); eb *= d(qfb[t].x); ob *= d(qfb[t].y);
+                                               ea *= d(wa.x); oa *= d(wa.y); eb *= d(wb.x); ob *= d(wb.y);
                                            }
                                        });
             } else {
@@ -632,7 +646,8 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                 lh += R;
             }
             stamp(2);
-        }
+        };
+        if (MODE != 1) front();
         c2 dtot;
         dtot.x = dtot.y = 0.0;
         c2 fy[4];                                                  // SLAB 1: this item's share of y at the four face planes (lines a / b)
@@ -669,6 +684,19 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                     qfb[2 * r] = ld16(xrow + lstride + m * (gp + G * r));
                     qfa[2 * r + 1] = ld16(xrow + m * (gq + G * r));
                     qfb[2 * r + 1] = ld16(xrow + lstride + m * (gq + G * r));
+                }
+            }
+            if (TURN && !FZ) {
+                // the forward half's u, same indices, requested now (the shifted variant requests it in its store phase, below)
+                const int gp = tid & ((1 << hbits) - 1), gq = (G - 1) - gp;
+                const double* urow = P.turn_u + tile_base(tile) + (act0 ? (size_t)(2 * (tid >> hbits)) * lstride : (size_t)0);
+                const int m = act0 ? 2 : 0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    ufa[TURN ? 2 * r : 0] = ld16(urow + m * (gp + G * r));
+                    ufb[TURN ? 2 * r : 0] = ld16(urow + lstride + m * (gp + G * r));
+                    ufa[TURN ? 2 * r + 1 : 0] = ld16(urow + m * (gq + G * r));
+                    ufb[TURN ? 2 * r + 1 : 0] = ld16(urow + lstride + m * (gq + G * r));
                 }
             }
         } else if (SPLIT) {
@@ -785,15 +813,39 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                                           const int t = FZ ? slot : 0;
                                           ea = P.fz_ct * ea + P.fz_cx * qfa[t].x; oa = P.fz_ct * oa + P.fz_cx * qfa[t].y;
                                           eb = P.fz_ct * eb + P.fz_cx * qfb[t].x; ob = P.fz_ct * ob + P.fz_cx * qfb[t].y;
-                                          ++slot;
                                       }
                                       st16(row + 2 * j, ea, oa);
                                       st16(row + lstride + 2 * j, eb, ob);
+                                      if (TURN) {
+                                          // the stored doubles are the forward half's samples of first-stage slot `slot`
+                                          const int t = TURN ? slot : 0;
+                                          pfa[t].x = ea; pfa[t].y = oa; pfb[t].x = eb; pfb[t].y = ob;
+                                          if (FZ) {
+                                              // shifted: u of this slot is requested only now that the slot's shift values are consumed --
+                                              // both streams held across the last stage take 278 VGPRs (spills); this way 2 tiles per CU
+                                              const double* urow = P.turn_u + tile_base(tile) + (size_t)(2 * pr) * lstride;
+                                              ufa[t] = ld16(urow + 2 * j);
+                                              ufb[t] = ld16(urow + lstride + 2 * j);
+                                          }
+                                      }
+                                      if (FZ || TURN) ++slot;
                                   });
             } else {
                 const unsigned o = 2u * (w & (npairs - 1));
                 dctc::fused_last(z + (size_t)(w & (npairs - 1)) * pstride, N, bits, w >> pbits,
                                  [&](int n, c2 v) { stg(o + (unsigned)n * estride, v); });
+            }
+        }
+        if (TURN) {
+            // every lane's last-stage LDS reads are done before the first stage of the forward half overwrites the tile
+            lds_barrier();
+            gout = P.turn_out + tile_base(tile);
+            front();
+            for (int w = tid; w < nmid; w += NT) {
+                const int pr = w >> hbits, t = w & ((1 << hbits) - 1);
+                const unsigned o = (unsigned)(2 * pr) * lstride;
+                dctc::fused_mid<0, false>(z + (size_t)pr * pstride, N, t, tw, ew, s0, s2, nold, [&](int k, c2 v) { st1(o + (unsigned)k, v); },
+                                          nosym, dtot);
             }
         }
     }
@@ -874,6 +926,15 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
         P.slab_hasb = sh->has_bottom ? 1 : 0; P.slab_hast = sh->has_top ? 1 : 0;
     }
     P.fz_v = nullptr; P.fzA = 1.0; P.fzB = P.fzC = 0.0; P.fz_cx = 0.0; P.fz_ct = 1.0; P.fz_store = nullptr;
+    P.turn_u = nullptr; P.turn_out = nullptr;
+    // x turnaround (DctFuse::xfwd): the inverse pass also runs the next application's x-forward pass on its own result
+    const bool want_turn = fz && inverse && fz->xfwd != nullptr;
+    if (want_turn) {
+        if (axis != 0 || fuse_scale != 0 || split || sh || !fz->u || !dct_axis_fused_ok(ctx, n0, n1, n2, 0, in, out, 0) ||
+            (((uintptr_t)fz->u | (uintptr_t)fz->xfwd | (uintptr_t)(fz->xadd ? fz->xadd : out)) & 15) != 0)
+            return set_error(ctx, "dct_axis_fft: the x turnaround needs the fused x-axis kernel (pw_fused_ok)");
+        P.turn_u = fz->u; P.turn_out = fz->xfwd; P.fzA = fz->A; P.fzB = fz->B; P.fzC = fz->C;
+    }
     // the pointwise work this pass is asked to take in: the factor (or the pre-axpy) on a forward pass, the axpy on an inverse one
     const bool want_fzs = fz && !inverse && fz->add != nullptr;
     const bool want_fz = fz && (inverse ? fz->xadd != nullptr : (fz->u != nullptr || want_fzs));
@@ -959,7 +1020,11 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 0, false, false, false, false, 1>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 1, false, false, false, false, 2>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 0, false, true, false, false, 1>),
-                             reinterpret_cast<const void*>(dct_fused_kernel<256, 1, false, true, false, false, 2>)};
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 1, false, true, false, false, 2>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, false, false, false, 0, false, true>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, false, false, true, 0, false, true>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, true, false, false, 0, false, true>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, true, false, true, 0, false, true>)};
         for (const void* f : fns) {
             const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
             if (e != hipSuccess) attr_err = e;
@@ -1008,7 +1073,12 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
 #define BK_DCT_LAUNCH(M, A, T) hipLaunchKernelGGL((dct_fused_kernel<256, M, A, T>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
 #define BK_DCT_LAUNCH_FZ(M, T) hipLaunchKernelGGL((dct_fused_kernel<256, M, true, T, false, true>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
 #define BK_DCT_LAUNCH_SLAB(M, T, S) hipLaunchKernelGGL((dct_fused_kernel<256, M, false, T, false, false, S>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
-        if (sh) {
+#define BK_DCT_LAUNCH_TURN(T, S) hipLaunchKernelGGL((dct_fused_kernel<256, 1, true, T, false, S, 0, false, true>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
+        if (want_turn) {
+            if (!(P.LT == 16 && mode == 1)) return set_error(ctx, "dct_axis_fft: x turnaround off the fused kernel's tiling");
+            if (want_fz) { if (ntm) BK_DCT_LAUNCH_TURN(true, true); else BK_DCT_LAUNCH_TURN(false, true); }
+            else { if (ntm) BK_DCT_LAUNCH_TURN(true, false); else BK_DCT_LAUNCH_TURN(false, false); }
+        } else if (sh) {
             if (mode == 1) { if (ntm) BK_DCT_LAUNCH_SLAB(1, true, 2); else BK_DCT_LAUNCH_SLAB(1, false, 2); }
             else { if (ntm) BK_DCT_LAUNCH_SLAB(0, true, 1); else BK_DCT_LAUNCH_SLAB(0, false, 1); }
         } else if (axis == 0 && want_fzs) {
@@ -1039,6 +1109,7 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
 #undef BK_DCT_LAUNCH
 #undef BK_DCT_LAUNCH_FZ
 #undef BK_DCT_LAUNCH_SLAB
+#undef BK_DCT_LAUNCH_TURN
         BK_HIP(ctx, hipGetLastError());
         if (trace) {
             // phase durations (wall_clock64 ticks of 10 ns) averaged over the tiles: stamps 0 start, 1 first stage done,

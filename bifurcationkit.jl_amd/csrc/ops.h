@@ -85,6 +85,9 @@ struct DctFuse {
     const double* add = nullptr;
     double cadd = 0.0;
     double* store = nullptr;
+    // x turnaround (bk_precond::apply_pw_chain, dct.hip: dct_apply_pw_chain): the x-INVERSE pass also multiplies what it stores by
+    // A + u (B + C u) and runs the next application's x-forward pass on it in the same tile residency, spectrum to xfwd
+    double* xfwd = nullptr;
 };
 int dct_apply(bk_ctx* ctx, DctPlan* p, const double* v, double* out, int* dot_blocks = nullptr, const DctFuse* fz = nullptr);
 // axis pass of the LDS FFT kernels (dct_fast.hip).  fuse_scale 0: plain, 1: forward + inverse symbol, 2: forward,
@@ -152,6 +155,15 @@ struct bk_op {              // a linear operator on (device vector [+ one host t
     // Newton-basis blocks of GMRES (solver.hip: arnoldi_block) apply (a0 - theta) x + a1 A x with a different theta per step:
     // true if a0 != 0 costs no extra pass over the vectors
     virtual bool shift_is_free() const { return false; }
+    // ... the s applications of one such block: outs[i] = (a0 - theta_i) x_i + a1 A x_i, x_0 = x, x_{i+1} = outs[i] (theta may be
+    // NULL: all 0).  Default: s apply calls; operators with a chained form override it.
+    virtual int apply_block(const double* x, int s, double a0, double a1, const double* theta, double* const* outs) {
+        for (int i = 0; i < s; ++i) {
+            const int e = apply(i == 0 ? x : outs[i - 1], nullptr, a0 - (theta ? theta[i] : 0.0), a1, outs[i], nullptr);
+            if (e != 0) return e;
+        }
+        return 0;
+    }
     // the Swift-Hohenberg Jacobian J = -L1 + diag(g(u)) with its two parts scaled separately,
     // out = a0 x + aL (-L1 x) + ag g(u) x; returns 1 if this operator is not of that form (nothing done)
     virtual int apply_parts(const double* x, double a0, double aL, double ag, double* out) { return 1; }
@@ -197,6 +209,10 @@ struct bk_precond {
     // Default: a pointwise pass, apply, an axpby; the spectral preconditioner fuses both into its first / last transform pass.
     virtual int apply_pw(const double* x, const bk::DctFuse& d, double cx, double ct, double* out);
     virtual bool pw_fused_ok(const double* x, const double* u, const double* out) const { return false; }
+    // A chain of s such applications, each on the previous one's output: x_0 = x, outs[i] = cx[i] x_i + ct Pl \ (d .* x_i),
+    // x_{i+1} = outs[i] (the Newton-basis block of solver.hip: arnoldi_block; outs[i] must not alias x_i).  Default: s apply_pw
+    // calls; the spectral preconditioner runs each x-inverse pass and the next x-forward pass as one (option dct_x_turnaround).
+    virtual int apply_pw_chain(const double* x, const bk::DctFuse& d, int s, const double* cx, double ct, double* const* outs);
     // the same for this rank's part of the plan alone (shape of the x passes, library-owned scratch; no caller pointer looked at) ...
     virtual bool pw_plan_ok() const { return false; }
     // ... and what the ranks agreed on, once per preconditioner (solver.hip: ShiftPrecOp::init_fold; -1: not asked yet).  The FORM of

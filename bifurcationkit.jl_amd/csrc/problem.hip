@@ -188,6 +188,11 @@ int bk_precond::apply_pw(const double* x, const bk::DctFuse& d, double cx, doubl
     return v_axpbyz(ctx, n, cx, x, ct, t, out);
 }
 
+int bk_precond::apply_pw_chain(const double* x, const bk::DctFuse& d, int s, const double* cx, double ct, double* const* outs) {
+    for (int i = 0; i < s; ++i) BK_TRY(apply_pw(i == 0 ? x : outs[i - 1], d, cx[i], ct, outs[i]));
+    return 0;
+}
+
 bool PdeJacobian::sh_state(const double** u_, double* l, double* nu) const {
     if (prob->desc.pde != BK_PDE_SH) return false;
     *u_ = u; *l = params[0]; *nu = params[1];

@@ -229,8 +229,9 @@ int arnoldi_block(bk_ctx* ctx, bk_op* A, Basis& B, int j, int s, double* Hraw, i
         !v_block_ok(ctx, n, B.V, B.ld))
         return 0;
     // p_{i+1} = (op_a0 + op_a1 A) p_i - theta_i p_i: the shift rides in the operator's own a0 term
-    for (int i = 0; i < s; ++i)
-        BK_TRY(A->apply(B.vec(j + i), nullptr, op_a0 - (theta ? theta[i] : 0.0), op_a1, B.vec(j + i + 1), nullptr));
+    double* outs[sstep::kS];
+    for (int i = 0; i < s; ++i) outs[i] = B.vec(j + i + 1);
+    BK_TRY(A->apply_block(B.vec(j), s, op_a0, op_a1, theta, outs));
     double D[33 * sstep::kR], T[sstep::kTri];
     PendingBlock local;
     PendingBlock* pb = defer ? defer : &local;
@@ -795,6 +796,7 @@ struct ShiftPrecOp : bk_op {
             }
         }
         mono_first = ctx->opt("gmres_monomial_shift", kMonomialShiftDefault) != 0.0;
+        chain = ctx->opt("dct_x_turnaround", 1.0) != 0.0;
         if (!tmode) return 0;
         // g(u) = l + 2 nu u - 3 u^2 (examples/SH3d.jl:50-53); factor = c0 + cg g = A + u (B + C u)
         const double cg = order == 0 ? 1.0 : a1, c0 = order == 0 ? pl_shift : a0 + a1 * pl_shift;
@@ -809,10 +811,19 @@ struct ShiftPrecOp : bk_op {
     double rearranged_origin() const override { return tmode ? (order == 0 ? 1.0 : a1) : 0.0; }
     double monomial_shift() const override { return mono_first ? rearranged_origin() : 0.0; }
     bool mono_first = false;      // option gmres_monomial_shift, read once per solve (init_fold)
+    bool chain = true;            // option dct_x_turnaround, read once per solve (init_fold)
     int apply(const double* x, const double*, double b0, double b1, double* out, double*) override {
         // out = b0 x + b1 * W(x)
         if (tmode) return P->apply_pw(x, pw, b0, b1, out);      // W = T (T'): see above
         return apply_chain(x, b0, b1, out);
+    }
+    // a Newton-basis block in stencil-free mode: the s applications as ONE preconditioner chain (bk_precond::apply_pw_chain), which
+    // lets the spectral preconditioner run each x-inverse pass together with the next application's x-forward pass
+    int apply_block(const double* x, int s, double b0, double b1, const double* theta, double* const* outs) override {
+        if (!tmode || !chain || s > sstep::kS) return bk_op::apply_block(x, s, b0, b1, theta, outs);
+        double cx[sstep::kS];
+        for (int i = 0; i < s; ++i) cx[i] = b0 - (theta ? theta[i] : 0.0);
+        return P->apply_pw_chain(x, pw, s, cx, b1, outs);
     }
     int apply_check(const double* x, const double*, double c0, double c1, double* out, double*) override {
         if (!tmode) return apply_chain(x, c0, c1, out);
