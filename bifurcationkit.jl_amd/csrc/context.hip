@@ -95,24 +95,20 @@ static void prof_resolve(bk_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------ reductions
+// op 1 (max) propagates NaN -- fmax would drop it (the partials of absmax_kernel: v_nrminf of a vector with a NaN is NaN)
+static __device__ __forceinline__ double stage2_combine(int op, double a, double b) { return op == 0 ? a + b : ((a != a || a > b) ? a : b); }
 __global__ void __launch_bounds__(256) reduce_stage2_kernel(const double* __restrict__ partials, int nblocks,
                                                             int nvals, int op, double* __restrict__ out) {
     const int v = blockIdx.x;
-    double acc = (op == 0) ? 0.0 : -1.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        const double x = partials[(size_t)b * nvals + v];
-        acc = (op == 0) ? acc + x : fmax(acc, x);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_down(acc, off, 64);
-        acc = (op == 0) ? acc + o : fmax(acc, o);
-    }
+    double acc = (op == 0) ? 0.0 : -INFINITY;
+    for (int b = threadIdx.x; b < nblocks; b += 256) acc = stage2_combine(op, acc, partials[(size_t)b * nvals + v]);
+    for (int off = 32; off > 0; off >>= 1) acc = stage2_combine(op, acc, __shfl_down(acc, off, 64));
     __shared__ double sm[4];
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         double r = sm[0];
-        for (int w = 1; w < 4; ++w) r = (op == 0) ? r + sm[w] : fmax(r, sm[w]);
+        for (int w = 1; w < 4; ++w) r = stage2_combine(op, r, sm[w]);
         out[v] = r;
     }
 }

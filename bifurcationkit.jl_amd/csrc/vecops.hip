@@ -62,9 +62,12 @@ __device__ __forceinline__ double wave_sum(double v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
     return v;
 }
+// max that PROPAGATES NaN (fmax drops it): norminf(x) = norm(x, Inf) of a vector with a NaN is NaN (src/LinearSolver.jl:4), so a Newton
+// started from a NaN state must not see a finite residual and report convergence
+__device__ __forceinline__ double max_nan(double a, double b) { return (a != a || a > b) ? a : b; }
 __device__ __forceinline__ double wave_max(double v) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+    for (int off = 32; off > 0; off >>= 1) v = max_nan(v, __shfl_down(v, off, 64));
     return v;
 }
 
@@ -359,12 +362,12 @@ __global__ void __launch_bounds__(kThreads) absmax_kernel(size_t n, const double
                                                           double* __restrict__ partials) {
     const size_t stride = (size_t)gridDim.x * kThreads;
     double m = 0.0;
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) m = fmax(m, fabs(x[i]));
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) m = max_nan(m, fabs(x[i]));
     __shared__ double sm[4];
     m = wave_max(m);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
     __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = fmax(fmax(sm[0], sm[1]), fmax(sm[2], sm[3]));
+    if (threadIdx.x == 0) partials[blockIdx.x] = max_nan(max_nan(sm[0], sm[1]), max_nan(sm[2], sm[3]));
 }
 
 // ------------------------------------------------------------------ fused multi-dot

@@ -26,6 +26,11 @@ def allreduce(user, buf, n, op):
         arr = np.ctypeslib.as_array(buf, shape=(n,))
         t = torch.from_numpy(arr.copy())
         dist.all_reduce(t, op=dist.ReduceOp.SUM if op == 0 else dist.ReduceOp.MAX, group=_group(user))
+        if op != 0:
+            # a NaN on any rank makes the max NaN (norminf = norm(x, Inf)); gloo's MAX keeps or drops it by operand order
+            nan = torch.from_numpy(np.isnan(arr).astype(np.float64))
+            dist.all_reduce(nan, op=dist.ReduceOp.MAX, group=_group(user))
+            t[nan != 0] = float("nan")
         arr[:] = t.numpy()
         return 0
     except Exception as e:  # pragma: no cover - surfaced as a library error
