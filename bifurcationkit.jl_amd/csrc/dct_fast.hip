@@ -390,7 +390,15 @@ __device__ __forceinline__ c2 lane_xor1(c2 v) { c2 r; r.x = lane_xor1(v.x); r.y 
 // last-stage outputs are the samples its first-stage item of the forward pass takes in (fused_last2 / fused_first2 walk the same
 // (pair, group) map), so they stay in registers, are multiplied by the MODE-0 FZ factor of u and run the forward transform in the same
 // residency: one read of Y (+ p_i) and u, one write of p_{i+1} and X_{i+1}, instead of two passes.
-template <int NT, int MODE, bool AX0, bool NTM, bool DOT = false, bool FZ = false, int SLAB = 0, bool FZS = false, bool TURN = false>   // MODE 0: forward, 1: inverse, 2: forward - symbol - inverse (AX0: 0 / 1 only)
+// CN (compile-time length, option dct_const_len): 0 = N, LT and the axis come from P; CN = 512 = the z round trip of the 512^3
+// product path, with N = 512, LT = 16 and axis 2 fixed, so that the stage loops, the trip counts of the work-item loops and the
+// index math of dct_core.h fold to constants.  The f64 expressions are the same, but this file compiles with contraction on, so
+// which products become FMAs is the compiler's choice per instantiation: that the results are the same bits is a property of
+// today's code generation, checked on the device by tests/test_gpu_dct_const_len.py, not guaranteed by construction.  (The x passes
+// at N = 512 did come out different in the last bit, and the y passes ran slower; both stay at the runtime length --
+// profiles/r8_const_len_isa.txt.)
+template <int NT, int MODE, bool AX0, bool NTM, bool DOT = false, bool FZ = false, int SLAB = 0, bool FZS = false, bool TURN = false,
+          int CN = 0>   // MODE 0: forward, 1: inverse, 2: forward - symbol - inverse (AX0: 0 / 1 only)
 __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P) {
     constexpr bool SPLIT = NT == 512;
     static_assert(!TURN || (MODE == 1 && AX0 && !DOT && SLAB == 0 && !FZS && !SPLIT), "TURN: the x inverse pass only");
@@ -398,10 +406,14 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
     static_assert(!SPLIT || (MODE == 2 && !AX0 && !FZ && SLAB == 0), "512 lanes: the z / y round trip only");
     static_assert(!FZ || (AX0 && MODE != 2), "FZ: x passes only");
     static_assert(SLAB == 0 || (!AX0 && !FZ && !DOT && ((SLAB == 1 && MODE == 0) || (SLAB == 2 && MODE == 1))), "SLAB: z halves only");
+    static_assert(CN == 0 || (CN == 512 && NT == 256 && MODE == 2 && !AX0), "compile-time length: the 256-lane z round trip at N = 512");
+    constexpr int CBITS = CN == 512 ? 9 : 0;
+    constexpr int CAX = CN == 0 ? -1 : 2;
     __shared__ double dsum[NT / 64];
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int N = P.N, bits = P.bits, G = N >> 3;
-    const int npairs = P.LT >> 1, pbits = P.ltbits - 1;
+    const int N = CN ? CN : P.N, bits = CN ? CBITS : P.bits, G = N >> 3;
+    const int LT = CN ? 16 : P.LT, npairs = LT >> 1, pbits = CN ? 3 : P.ltbits - 1;
+    const int axis = CN ? CAX : P.axis;
     const int pstride = N + 1;
     c2* z = reinterpret_cast<c2*>(smem);
     const int twl = dctc::tw_len(N), ewl = dctc::ew_len(N);
@@ -410,20 +422,31 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
     double* lamk = reinterpret_cast<double*>(ew + ewl + 1);   // MODE 2 / SLAB: eigenvalues along the transform axis
     double* phik = lamk + N;                                  // SLAB: [2][N] local basis at planes 0, 1
     const int tid = threadIdx.x;
+    // work-item loop `for (w = tid; w < n; w += NT)`: with a compile-time length the trip count is a constant (at CN = 512 every n
+    // is a multiple of NT: 512 group items, 512 first-stage items, 256 merged-middle items).  Two-trip loops stay loops:
+    // unrolled, they cost 27 VGPRs more in the z round trip (222) and double the code of the middle stages
+    auto items = [&](int n, auto&& body) {
+        if constexpr (CN != 0) {
+#pragma nounroll
+            for (int i = 0; i < n / NT; ++i) body(tid + i * NT);
+        } else {
+            for (int w = tid; w < n; w += NT) body(w);
+        }
+    };
     const int nfirst = AX0 ? npairs * (G >> 1) : npairs * G;  // work items of the outer stages ...
     const int nmid = npairs * (G >> 1);                       // ... and of the merged middle
     const int hbits = bits - 4;                               // log2(G / 2)
     // element stride along the transform axis; the host guarantees that the array is < 4 GiB, so that every access is
     // (uniform tile base) + (32-bit per-lane byte offset) -- one VGPR per address instead of two
-    const unsigned estride = AX0 ? 1u : (P.axis == 1 ? (unsigned)P.n0 : (unsigned)P.n0 * (unsigned)P.n1);
-    const unsigned lstride = AX0 ? (unsigned)P.n0 : 1u;       // line a -> line b of a pair
+    const unsigned estride = AX0 ? 1u : (axis == 1 ? (unsigned)P.n0 : (unsigned)P.n0 * (unsigned)P.n1);
+    const unsigned lstride = AX0 ? (unsigned)N : 1u;          // line a -> line b of a pair
 
     // tile -> (x0, other, element offsets of its input / output)
-    auto tile_x0 = [&](int tile) { return AX0 ? 0 : (tile % P.tiles_x) * P.LT; };
+    auto tile_x0 = [&](int tile) { return AX0 ? 0 : (tile % P.tiles_x) * LT; };
     auto tile_other = [&](int tile) { return AX0 ? 0 : tile / P.tiles_x; };     // i2 (axis 1) or i1 (axis 2)
     auto tile_base = [&](int tile) {
         const size_t x0 = (size_t)tile_x0(tile), other = (size_t)tile_other(tile);
-        return AX0 ? (size_t)tile * P.LT * P.n0 : (P.axis == 1 ? x0 + (size_t)P.n0 * P.n1 * other : x0 + (size_t)P.n0 * other);
+        return AX0 ? (size_t)tile * LT * N : (axis == 1 ? x0 + (size_t)P.n0 * P.n1 * other : x0 + (size_t)P.n0 * other);
     };
     // distributed plan: one side of the y pass lives in the all-to-all block layout (dct.hip, dct_apply_dist)
     auto tile_sbase = [&](int tile) { return (size_t)tile_x0(tile) + (size_t)tile_other(tile) * P.split_plane; };
@@ -454,11 +477,12 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
     };
 
 
-    const double s0 = sqrt(1.0 / N), s2 = sqrt(2.0 / N);
+    // (from P.N also at a compile-time length: the scales are computed on the device, as in the runtime-length kernels)
+    const double s0 = sqrt(1.0 / P.N), s2 = sqrt(2.0 / P.N);
     auto middle = [&](int lh, int R, bool inv) {
         const int gbits = bits - R;
         const int ngr = npairs << gbits;
-        for (int w = tid; w < ngr; w += NT) {
+        items(ngr, [&](int w) {
             c2* zp = z + (size_t)(w >> gbits) * pstride;
             const int g = w & ((1 << gbits) - 1);
             if (!inv) {
@@ -470,7 +494,7 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                 else if (R == 2) dctc::dif_group_inv<2>(zp, bits, lh, g, tw);
                 else dctc::dif_group_inv<1>(zp, bits, lh, g, tw);
             }
-        }
+        });
         lds_barrier();
     };
     auto nold = [](int, int) { c2 r; r.x = 0.0; r.y = 0.0; return r; };
@@ -578,7 +602,7 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
         // puts the short table loads behind 16 HBM loads per lane.
         for (int q = tid; q < twl + ewl; q += NT) tw[q] = reinterpret_cast<const c2*>(P.twid)[q];
         if (MODE == 2 || SLAB)
-            for (int q = tid; q < N; q += NT) lamk[q] = (P.axis == 1 ? P.lam1 : P.lam2)[q];
+            for (int q = tid; q < N; q += NT) lamk[q] = (axis == 1 ? P.lam1 : P.lam2)[q];
         if (SLAB)
             for (int q = tid; q < 2 * N; q += NT) phik[q] = P.phi[q];
         issue(tile);
@@ -593,8 +617,8 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
         double ca = 0.0, cb = 0.0, lo2 = 0.0;
         if (MODE == 2 || SLAB) {
             const int i0 = x0 + 2 * ((SPLIT ? tid >> 1 : tid) & (npairs - 1));      // (SPLIT: lanes 2w, 2w + 1 share the item w)
-            const double l1 = P.axis == 1 ? 0.0 : P.lam1[other];
-            lo2 = P.axis == 1 ? (P.lam2 ? P.lam2[other] : 0.0) : 0.0;
+            const double l1 = axis == 1 ? 0.0 : P.lam1[other];
+            lo2 = axis == 1 ? (P.lam2 ? P.lam2[other] : 0.0) : 0.0;
             ca = 1.0 + P.lam0[i0] + l1;
             cb = 1.0 + P.lam0[i0 + 1] + l1;
         }
@@ -721,14 +745,16 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
             }
             dctc::mid_half_inv(zp, N, t, h, tw, v);
         } else
-        for (int w = tid; w < nmid; w += NT) {
+        items(nmid, [&](int w) {
             const int pr = AX0 ? w >> hbits : w & (npairs - 1), t = AX0 ? w & ((1 << hbits) - 1) : w >> pbits;
             const unsigned o = AX0 ? (unsigned)(2 * pr) * lstride : 2u * pr;
             c2* zp = z + (size_t)pr * pstride;
             if (MODE == 2) {
                 auto sym = [&](int k) {
                     const double lk = lamk[k];
-                    const double sa = ca + lk + lo2, sb = cb + lk + lo2;
+                    // z pass at a compile-time length: lo2 is 0 and (ca + lk) + 0.0 differs from ca + lk at most in the sign of a zero,
+                    // which sa * sa does not see
+                    const double sa = CAX == 2 ? ca + lk : ca + lk + lo2, sb = CAX == 2 ? cb + lk : cb + lk + lo2;
                     c2 r; r.x = rcp_nr(sa * sa + P.shift, 2); r.y = rcp_nr(sb * sb + P.shift, 2); return r;
                 };
                 dctc::fused_mid<2, DOT>(zp, N, t, tw, ew, s0, s2, nold, nost, sym, dtot);
@@ -749,7 +775,7 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                 else if (P.split == 1) dctc::fused_mid<0, false>(zp, N, t, tw, ew, s0, s2, nold, [&](int k, c2 v) { stg(o + P.kmap[k], v); }, nosym, dtot);
                 else dctc::fused_mid<0, false>(zp, N, t, tw, ew, s0, s2, nold, [&](int k, c2 v) { stg(o + (unsigned)k * estride, v); }, nosym, dtot);
             }
-        }
+        });
         stamp(3);
         if (MODE == 0 && SLAB == 1) {
             // the items of one line pair (same pr, t = 0 .. G/2 - 1) sit npairs lanes apart: their shares are summed through the tile's
@@ -802,7 +828,7 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
             top -= R;
         }
         stamp(5);
-        for (int w = tid; w < nfirst; w += NT) {
+        items(nfirst, [&](int w) {
             if (AX0) {
                 const int pr = w >> hbits;
                 double* row = gout + (size_t)(2 * pr) * lstride;
@@ -835,18 +861,18 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                 dctc::fused_last(z + (size_t)(w & (npairs - 1)) * pstride, N, bits, w >> pbits,
                                  [&](int n, c2 v) { stg(o + (unsigned)n * estride, v); });
             }
-        }
+        });
         if (TURN) {
             // every lane's last-stage LDS reads are done before the first stage of the forward half overwrites the tile
             lds_barrier();
             gout = P.turn_out + tile_base(tile);
             front();
-            for (int w = tid; w < nmid; w += NT) {
+            items(nmid, [&](int w) {
                 const int pr = w >> hbits, t = w & ((1 << hbits) - 1);
                 const unsigned o = (unsigned)(2 * pr) * lstride;
                 dctc::fused_mid<0, false>(z + (size_t)pr * pstride, N, t, tw, ew, s0, s2, nold, [&](int k, c2 v) { st1(o + (unsigned)k, v); },
                                           nosym, dtot);
-            }
+            });
         }
     }
     if (P.trace) { __builtin_amdgcn_s_waitcnt(0); stamp(6); }
@@ -879,6 +905,36 @@ inline int choose_lt(int N, int axis, int n0, size_t rows, bool wide = false) {
         if (lt > n0e) lt = n0e;
     }
     return lt < 2 ? 2 : lt;
+}
+
+// The 256-lane fused passes: x forward / inverse (plain, FZ, FZS, TURN shifted / unshifted), y forward / inverse and the z round trip
+// with and without DOT at the runtime length (CN = 0); the z round trip also at the compile-time length (CN = 512) -- NTM on and off.
+// The slab halves and the 512-lane round trip are launched by the caller.
+template <int MODE, bool AX0, bool DOT, bool FZ, bool FZS, bool TURN, int CN>
+void launch_fused_ntm(const FftK& P, unsigned grid, size_t lds, hipStream_t st, bool ntm) {
+    if (ntm) hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, true, DOT, FZ, 0, FZS, TURN, CN>), dim3(grid), dim3(256), lds, st, P);
+    else hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, false, DOT, FZ, 0, FZS, TURN, CN>), dim3(grid), dim3(256), lds, st, P);
+}
+
+void launch_fused_x(const FftK& P, unsigned grid, size_t lds, hipStream_t st, int mode, bool ntm, bool turn, bool fz, bool fzs) {
+    //                                        MODE AX0    DOT    FZ     FZS    TURN
+    if (turn && fz) launch_fused_ntm<1, true, false, true, false, true, 0>(P, grid, lds, st, ntm);
+    else if (turn) launch_fused_ntm<1, true, false, false, false, true, 0>(P, grid, lds, st, ntm);
+    else if (fzs) launch_fused_ntm<0, true, false, true, true, false, 0>(P, grid, lds, st, ntm);
+    else if (fz && mode == 1) launch_fused_ntm<1, true, false, true, false, false, 0>(P, grid, lds, st, ntm);
+    else if (fz) launch_fused_ntm<0, true, false, true, false, false, 0>(P, grid, lds, st, ntm);
+    else if (mode == 1) launch_fused_ntm<1, true, false, false, false, false, 0>(P, grid, lds, st, ntm);
+    else launch_fused_ntm<0, true, false, false, false, false, 0>(P, grid, lds, st, ntm);
+}
+
+void launch_fused_yz(const FftK& P, unsigned grid, size_t lds, hipStream_t st, int mode, bool ntm, bool dot, bool const_len) {
+    if (mode == 2 && const_len) {
+        if (dot) launch_fused_ntm<2, false, true, false, false, false, 512>(P, grid, lds, st, ntm);
+        else launch_fused_ntm<2, false, false, false, false, false, 512>(P, grid, lds, st, ntm);
+    } else if (mode == 2 && dot) launch_fused_ntm<2, false, true, false, false, false, 0>(P, grid, lds, st, ntm);
+    else if (mode == 2) launch_fused_ntm<2, false, false, false, false, false, 0>(P, grid, lds, st, ntm);
+    else if (mode == 1) launch_fused_ntm<1, false, false, false, false, false, 0>(P, grid, lds, st, ntm);
+    else launch_fused_ntm<0, false, false, false, false, false, 0>(P, grid, lds, st, ntm);
 }
 
 }  // namespace
@@ -1024,7 +1080,12 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, false, false, false, 0, false, true>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, false, false, true, 0, false, true>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, true, false, false, 0, false, true>),
-                             reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, true, false, true, 0, false, true>)};
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, true, false, true, 0, false, true>),
+                             // compile-time length (launch_fused_yz)
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, false, true, false, 0, false, false, 512>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, false, false, false, 0, false, false, 512>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, true, true, false, 0, false, false, 512>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, true, false, false, 0, false, false, 512>)};
         for (const void* f : fns) {
             const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
             if (e != hipSuccess) attr_err = e;
@@ -1070,46 +1131,31 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
         // tiles of exactly 512 first-stage items = 256 merged-middle items
         const bool split512 = mode == 2 && axis != 0 && (size_t)(P.LT / 2) * (P.N / 8) == 512 &&
                               ctx->opt("dct_rt_lanes", kRoundTripLanesDefault) == 512.0;
-#define BK_DCT_LAUNCH(M, A, T) hipLaunchKernelGGL((dct_fused_kernel<256, M, A, T>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
-#define BK_DCT_LAUNCH_FZ(M, T) hipLaunchKernelGGL((dct_fused_kernel<256, M, true, T, false, true>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
+        const bool dot = mode == 2 && dot_blocks && (size_t)grid <= kPartialDoubles && ctx->opt("dct_fused_dot", 1.0) != 0.0;
+        if (dot) { P.dotp = ctx->d_partials; *dot_blocks = (int)grid; }
+        if (want_turn && !(P.LT == 16 && mode == 1)) return set_error(ctx, "dct_axis_fft: x turnaround off the fused kernel's tiling");
+        // compile-time length (option dct_const_len): the z round trip at the 512^3 product path's tiling -- N = 512, LT = 16, axis 2 --
+        // and neither the block layout nor the slab halves nor the 512-lane kernel
+        const bool const_len = ctx->opt("dct_const_len", 1.0) != 0.0 && mode == 2 && axis == 2 && P.N == 512 && P.LT == 16 && !split &&
+                               !sh && !split512;
 #define BK_DCT_LAUNCH_SLAB(M, T, S) hipLaunchKernelGGL((dct_fused_kernel<256, M, false, T, false, false, S>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
-#define BK_DCT_LAUNCH_TURN(T, S) hipLaunchKernelGGL((dct_fused_kernel<256, 1, true, T, false, S, 0, false, true>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
-        if (want_turn) {
-            if (!(P.LT == 16 && mode == 1)) return set_error(ctx, "dct_axis_fft: x turnaround off the fused kernel's tiling");
-            if (want_fz) { if (ntm) BK_DCT_LAUNCH_TURN(true, true); else BK_DCT_LAUNCH_TURN(false, true); }
-            else { if (ntm) BK_DCT_LAUNCH_TURN(true, false); else BK_DCT_LAUNCH_TURN(false, false); }
-        } else if (sh) {
+        if (sh) {
             if (mode == 1) { if (ntm) BK_DCT_LAUNCH_SLAB(1, true, 2); else BK_DCT_LAUNCH_SLAB(1, false, 2); }
             else { if (ntm) BK_DCT_LAUNCH_SLAB(0, true, 1); else BK_DCT_LAUNCH_SLAB(0, false, 1); }
-        } else if (axis == 0 && want_fzs) {
-            if (ntm) hipLaunchKernelGGL((dct_fused_kernel<256, 0, true, true, false, true, 0, true>), dim3(grid), dim3(256), ldsf, ctx->stream, P);
-            else hipLaunchKernelGGL((dct_fused_kernel<256, 0, true, false, false, true, 0, true>), dim3(grid), dim3(256), ldsf, ctx->stream, P);
-        } else if (axis == 0 && want_fz) {
-            if (mode == 1) { if (ntm) BK_DCT_LAUNCH_FZ(1, true); else BK_DCT_LAUNCH_FZ(1, false); }
-            else { if (ntm) BK_DCT_LAUNCH_FZ(0, true); else BK_DCT_LAUNCH_FZ(0, false); }
-        } else if (axis == 0) {
-            if (mode == 1) { if (ntm) BK_DCT_LAUNCH(1, true, true); else BK_DCT_LAUNCH(1, true, false); }
-            else { if (ntm) BK_DCT_LAUNCH(0, true, true); else BK_DCT_LAUNCH(0, true, false); }
-        } else if (mode == 2 && dot_blocks && (size_t)grid <= kPartialDoubles && ctx->opt("dct_fused_dot", 1.0) != 0.0) {
-            P.dotp = ctx->d_partials;
-            if (split512) {
+        } else if (split512) {
+            if (dot) {
                 if (ntm) hipLaunchKernelGGL((dct_fused_kernel<512, 2, false, true, true>), dim3(grid), dim3(512), ldsf, ctx->stream, P);
                 else hipLaunchKernelGGL((dct_fused_kernel<512, 2, false, false, true>), dim3(grid), dim3(512), ldsf, ctx->stream, P);
             } else {
-                if (ntm) hipLaunchKernelGGL((dct_fused_kernel<256, 2, false, true, true>), dim3(grid), dim3(256), ldsf, ctx->stream, P);
-                else hipLaunchKernelGGL((dct_fused_kernel<256, 2, false, false, true>), dim3(grid), dim3(256), ldsf, ctx->stream, P);
+                if (ntm) hipLaunchKernelGGL((dct_fused_kernel<512, 2, false, true>), dim3(grid), dim3(512), ldsf, ctx->stream, P);
+                else hipLaunchKernelGGL((dct_fused_kernel<512, 2, false, false>), dim3(grid), dim3(512), ldsf, ctx->stream, P);
             }
-            *dot_blocks = (int)grid;
-        } else if (mode == 2 && split512) {
-            if (ntm) hipLaunchKernelGGL((dct_fused_kernel<512, 2, false, true>), dim3(grid), dim3(512), ldsf, ctx->stream, P);
-            else hipLaunchKernelGGL((dct_fused_kernel<512, 2, false, false>), dim3(grid), dim3(512), ldsf, ctx->stream, P);
-        } else if (mode == 2) { if (ntm) BK_DCT_LAUNCH(2, false, true); else BK_DCT_LAUNCH(2, false, false); }
-        else if (mode == 1) { if (ntm) BK_DCT_LAUNCH(1, false, true); else BK_DCT_LAUNCH(1, false, false); }
-        else { if (ntm) BK_DCT_LAUNCH(0, false, true); else BK_DCT_LAUNCH(0, false, false); }
-#undef BK_DCT_LAUNCH
-#undef BK_DCT_LAUNCH_FZ
+        } else if (axis == 0) {
+            launch_fused_x(P, grid, ldsf, ctx->stream, mode, ntm, want_turn, want_fz, want_fzs);
+        } else {
+            launch_fused_yz(P, grid, ldsf, ctx->stream, mode, ntm, dot, const_len);
+        }
 #undef BK_DCT_LAUNCH_SLAB
-#undef BK_DCT_LAUNCH_TURN
         BK_HIP(ctx, hipGetLastError());
         if (trace) {
             // phase durations (wall_clock64 ticks of 10 ns) averaged over the tiles: stamps 0 start, 1 first stage done,
@@ -1134,7 +1180,7 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
             fprintf(stderr, "dct_trace axis=%d mode=%d tiles=%u span=%.1fus  phases[us]:", axis, P.roundtrip ? 2 : P.inverse, grid,
                     (tmax - tmin) * 0.01);
             for (int i = 1; i < 7; ++i) fprintf(stderr, " %d:%.2f", i, acc[i] / grid * 0.01);
-            fprintf(stderr, "\n");
+            fprintf(stderr, " const_len=%d\n", const_len ? P.N : 0);
         }
         return 0;
     }
