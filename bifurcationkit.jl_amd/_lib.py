@@ -178,6 +178,15 @@ SIGNATURES = {
     "bk_newton_palc": (I, [VP, VP, VP, c_double_p, VP, D, VP, D, D, D, c_double_p, I, I, D, D,
                            C.POINTER(NewtonOpts), C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP,
                            C.POINTER(NewtonResult)]),
+    "bk_d2f": (I, [VP, VP, c_double_p, I, VP, VP, VP]),
+    "bk_djdp": (I, [VP, VP, c_double_p, I, I, VP, VP]),
+    "bk_fold_contract": (I, [VP, VP, c_double_p, I, I, VP, VP, I, C.POINTER(VP), c_double_p]),
+    "bk_fold_terms": (I, [VP, VP, VP, c_double_p, I, I, VP, VP, C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP, VP, VP,
+                          c_double_p, c_double_p, c_int_p, c_int_p]),
+    "bk_fold_linsolve": (I, [VP, VP, VP, c_double_p, I, I, VP, VP, I, C.POINTER(VP), c_double_p, C.POINTER(GmresOpts), VP,
+                             C.POINTER(VP), c_double_p, c_int_p, c_int_p]),
+    "bk_newton_fold": (I, [VP, VP, VP, c_double_p, c_double_p, I, I, VP, VP, C.POINTER(NewtonOpts), C.POINTER(BorderingOpts),
+                           C.POINTER(GmresOpts), VP, VP, VP, c_double_p, C.POINTER(NewtonResult)]),
 }
 
 _lib = None

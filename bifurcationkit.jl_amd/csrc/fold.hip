@@ -1,0 +1,415 @@
+// Minimally augmented fold formulation, matrix-free: src/codim2/MinAugFold.jl on the preconditioned GMRES path.
+//
+//   unknowns (x, p), G(x, p) = (F(x, p), sigma(x, p)),  [J a; b' 0][v; sigma] = [0; 1],  [J' b; a' 0][w; sigma2] = [0; 1]
+//
+// The Swift-Hohenberg problems are symmetric (J' = J, :79-84), so the adjoint system is the same bordered solve with a and b
+// exchanged, and no solve at all when a and b are the same vector.  Their second derivative d2F(x, p)[dx1, dx2] =
+// h(u) dx1 dx2 and the parameter derivative of J, dJ/dp = diag(g_p(u)), are pointwise polynomials (vecops.hip: fold_pw_kernel,
+// fold_contract_kernel):
+//   BK_PDE_SH   h = 2 nu - 6 u                (examples/SH2d-fronts.jl:40)   g_l = 1,  g_nu = 2 u
+//   BK_PDE_SH1D h = 6 nu u - 20 u^3           (examples/SHpde_snaking.jl:26) g_lam = 1, g_nu = 3 u^2
+// so sigma_p = -<w, dJ/dp v> (:90-95), dpF (:88-89) and sigma_x . X (:153-157) are evaluated analytically: the reference's
+// central differences equal them up to rounding.
+#include <cmath>
+
+#include "common.h"
+#include "ops.h"
+#include "stream.h"
+
+namespace bk {
+
+namespace {
+
+// ------------------------------------------------------------------ kernels
+// Pointwise polynomial factors c[0] + u (c[1] + u (c[2] + u c[3])) of d2F (h) and dJ/dp (g), evaluated in this one fixed
+// Horner order (tests/test_gpu_fold.py restates it).
+struct FoldPoly { double h[4]; double g[4]; };
+__device__ __forceinline__ double fold_poly(const double* c, double u) { return c[0] + u * (c[1] + u * (c[2] + u * c[3])); }
+
+// out = (f(u) x1) x2, or f(u) x1 when x2 is NULL: d2F(u)[x1, x2] and dJ/dp(u) x1 (bk_d2f, bk_djdp)
+__global__ void __launch_bounds__(kThreads) fold_pw_kernel(size_t n, const double* __restrict__ u, FoldPoly P,
+                                                           const double* __restrict__ x1, const double* __restrict__ x2,
+                                                           double* __restrict__ out) {
+    const size_t stride = (size_t)gridDim.x * kThreads;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) {
+        const double f = fold_poly(P.h, u[i]) * x1[i];
+        out[i] = x2 ? f * x2[i] : f;
+    }
+}
+
+// One pass over u, v, w and M vectors X_k:  s_k = sum w h(u) v X_k (k < M),  s_M = sum w g(u) v  -- the sigma_x terms of
+// foldMALinearSolver (src/codim2/MinAugFold.jl:153-157) and sigma_p (:94-95) without materialising d2F(x, p)[X_k, v].
+// M + 1 partial sums per workgroup; the second stage (reduce_finish) keeps the fixed order, so the sums are bitwise the same
+// run to run and, all-reduced, on every rank.
+template <int M, int VEC, bool NTH>
+__global__ void __launch_bounds__(kThreads) fold_contract_kernel(size_t n, const double* __restrict__ pu,
+                                                                 const double* __restrict__ pv, const double* __restrict__ pw,
+                                                                 const double* __restrict__ X0, const double* __restrict__ X1,
+                                                                 const double* __restrict__ X2, FoldPoly P,
+                                                                 double* __restrict__ partials) {
+    double s[M + 1];
+#pragma unroll
+    for (int k = 0; k <= M; ++k) s[k] = 0.0;
+    const double* X[3] = {X0, X1, X2};
+    auto elem = [&](double uu, double vv, double ww, const double* xs) {
+        const double t = ww * vv;
+        const double th = t * fold_poly(P.h, uu);
+#pragma unroll
+        for (int k = 0; k < M; ++k) s[k] = fma(th, xs[k], s[k]);
+        s[M] = fma(t, fold_poly(P.g, uu), s[M]);
+    };
+    if (VEC == 2) {
+        stream_loop<2>(n >> 1, [&](auto uc, size_t i0, size_t st) {
+            constexpr int UU = decltype(uc)::value;
+            double2 uv[UU], vv[UU], wv[UU], xv[M > 0 ? M : 1][UU];
+#pragma unroll
+            for (int q = 0; q < UU; ++q) {
+                uv[q] = ld2<NTH>(pu, i0 + q * st);
+                vv[q] = ld2<NTH>(pv, i0 + q * st);
+                wv[q] = ld2<NTH>(pw, i0 + q * st);
+#pragma unroll
+                for (int k = 0; k < M; ++k) xv[k][q] = ld2<NTH>(X[k], i0 + q * st);
+            }
+#pragma unroll
+            for (int q = 0; q < UU; ++q) {
+                double xa[M > 0 ? M : 1], xb[M > 0 ? M : 1];
+#pragma unroll
+                for (int k = 0; k < M; ++k) { xa[k] = xv[k][q].x; xb[k] = xv[k][q].y; }
+                elem(uv[q].x, vv[q].x, wv[q].x, xa);
+                elem(uv[q].y, vv[q].y, wv[q].y, xb);
+            }
+        });
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+            const size_t i = n - 1;
+            double xa[M > 0 ? M : 1];
+#pragma unroll
+            for (int k = 0; k < M; ++k) xa[k] = X[k][i];
+            elem(pu[i], pv[i], pw[i], xa);
+        }
+    } else {
+        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) {
+            double xa[M > 0 ? M : 1];
+#pragma unroll
+            for (int k = 0; k < M; ++k) xa[k] = X[k][i];
+            elem(pu[i], pv[i], pw[i], xa);
+        }
+    }
+    __shared__ double sm[M + 1][4];
+    const int lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k <= M; ++k) {
+        const double t = wave_sum(s[k]);
+        if (lane == 0) sm[k][wv_] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x <= M) {
+        const int k = threadIdx.x;
+        partials[(size_t)blockIdx.x * (M + 1) + k] = (sm[k][0] + sm[k][1]) + (sm[k][2] + sm[k][3]);
+    }
+}
+
+static int v_fold_pw(bk_ctx* ctx, size_t n, const double* u, const double c[4], const double* x1, const double* x2, double* out) {
+    if (n == 0) return 0;
+    FoldPoly P{};
+    for (int i = 0; i < 4; ++i) P.h[i] = c[i];
+    ProfScope ps(ctx, "blas1", 8.0 * n * (x2 ? 4 : 3));
+    hipLaunchKernelGGL(fold_pw_kernel, dim3(grid_for(n, 1, 4096)), dim3(kThreads), 0, ctx->stream, n, u, P, x1, x2, out);
+    BK_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+static int v_fold_contract(bk_ctx* ctx, size_t n, const double* u, const double* v, const double* w, int m, const double* const* X,
+                    const double h[4], const double g[4], double* out) {
+    if (m < 0 || m > 3) return set_error(ctx, "v_fold_contract: 0 <= m <= 3 (got %d)", m);
+    FoldPoly P{};
+    for (int i = 0; i < 4; ++i) { P.h[i] = h[i]; P.g[i] = g[i]; }
+    const double* x[3] = {nullptr, nullptr, nullptr};
+    bool vec = aligned16(u) && aligned16(v) && aligned16(w);
+    for (int k = 0; k < m; ++k) { x[k] = X[k]; vec = vec && aligned16(X[k]); }
+    const bool nth = vec && nt_hint(ctx, n);
+    const int grid = grid_for(n, vec ? 4 : 1, kRedBlocks);        // stream_loop<2>: 2 x 16 B per lane per chunk
+    {
+        ProfScope ps(ctx, "fold_contract", 8.0 * n * (3 + m));
+#define BK_FC(M)                                                                                                                                     \
+    do {                                                                                                                                             \
+        if (nth) hipLaunchKernelGGL((fold_contract_kernel<M, 2, true>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, u, v, w, x[0], x[1], x[2], P, ctx->d_partials); \
+        else if (vec) hipLaunchKernelGGL((fold_contract_kernel<M, 2, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, u, v, w, x[0], x[1], x[2], P, ctx->d_partials); \
+        else hipLaunchKernelGGL((fold_contract_kernel<M, 1, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, u, v, w, x[0], x[1], x[2], P, ctx->d_partials); \
+    } while (0)
+        switch (m) {
+            case 0: BK_FC(0); break;
+            case 1: BK_FC(1); break;
+            case 2: BK_FC(2); break;
+            default: BK_FC(3); break;
+        }
+#undef BK_FC
+        BK_HIP(ctx, hipGetLastError());
+    }
+    BK_TRY(reduce_finish(ctx, grid, m + 1, 0));
+    for (int k = 0; k <= m; ++k) out[k] = ctx->h_red[k];
+    return 0;
+}
+
+// ------------------------------------------------------------------ the formulation
+// polynomial coefficients (c0 + u (c1 + u (c2 + u c3))) of h(u) and g_ipar(u); an error for problems without the formulation
+int fold_polys(bk_problem* prob, const double* params, int nparams, int ipar, double h[4], double g[4]) {
+    bk_ctx* ctx = prob->ctx;
+    const int pde = prob->desc.pde;
+    if (pde != BK_PDE_SH && pde != BK_PDE_SH1D)
+        return set_error(ctx, "fold: the minimally augmented fold formulation is available for BK_PDE_SH and BK_PDE_SH1D only "
+                              "(symmetric Jacobian with an analytic Hessian), not for problem kind %d", pde);
+    if (nparams < 2 || nparams > BK_MAX_PARAMS) return set_error(ctx, "fold: the SH problems take params = {l | lambda, nu}");
+    if (ipar < 0 || ipar > 1) return set_error(ctx, "fold: bad parameter index %d", ipar);
+    const double nu = params[1];
+    for (int i = 0; i < 4; ++i) h[i] = g[i] = 0.0;
+    if (pde == BK_PDE_SH) {
+        h[0] = 2.0 * nu; h[1] = -6.0;
+        if (ipar == 0) g[0] = 1.0; else g[1] = 2.0;
+    } else {
+        h[1] = 6.0 * nu; h[3] = -20.0;
+        if (ipar == 0) g[0] = 1.0; else g[2] = 3.0;
+    }
+    return 0;
+}
+
+int norm_fold(bk_ctx* ctx, size_t n, const double* f, double sigma, bool inf, double* out) {
+    double r;
+    if (inf) {
+        BK_TRY(v_nrminf(ctx, n, f, &r));
+        *out = (r != r || r > std::fabs(sigma)) ? r : std::fabs(sigma);          // norminf of BorderedArray(F, sigma)
+    } else {
+        BK_TRY(v_nrm2(ctx, n, f, &r));
+        *out = std::sqrt(r * r + sigma * sigma);
+    }
+    return 0;
+}
+
+// _compute_bordered_vectors (:54-69): v from [J a; b' 0][v; sigma] = [0; 1] with the BorderingBLS path; w from the adjoint
+// system [J b; a' 0][w; sigma2] = [0; 1] (J' = J), or w = v when a and b are the same vector.  sigma = the border of the first.
+int fold_terms(bk_ctx* ctx, bk_op* J, size_t n, const double* a, const double* b, const bk_bordering_opts& bo,
+               const bk_gmres_opts& lo, bk_precond* pl, double* zero, double* v, double* w, double* sigma, int* cv, int it[2]) {
+    BK_TRY(v_zero(ctx, n, zero));
+    int c1 = 0, c2 = 1, i1[2] = {0, 0}, i2[2] = {0, 0};
+    BK_TRY(bls_bordering(ctx, J, a, b, 0.0, zero, 1.0, 1.0, 1.0, false, 0.0, 1.0, bo, lo, pl, v, sigma, &c1, i1));
+    if (a == b) {
+        if (w != v) BK_TRY(v_copy(ctx, n, v, w));
+    } else {
+        double s2 = 0.0;
+        BK_TRY(bls_bordering(ctx, J, b, a, 0.0, zero, 1.0, 1.0, 1.0, false, 0.0, 1.0, bo, lo, pl, w, &s2, &c2, i2));
+    }
+    *cv = c1 & c2;
+    it[0] = i1[0] + i1[1];
+    it[1] = i2[0] + i2[1];
+    return 0;
+}
+
+// foldMALinearSolver, usehessian branch (:146-164), for nrhs right-hand sides sharing the J \ dpF solve:
+//   x1_k = J \ rhsu_k, x2 = J \ dpF, sx_k = -<w, d2F[x1_k, v]>, sx2 = -<w, d2F[x2, v]>, sp = -<w, dJ/dp v>,
+//   dsig_k = (rhsp_k - sx_k) / (sp - sx2), dX_k = x1_k - dsig_k x2.
+// The sums come from ONE fused pass (v_fold_contract) instead of d2F into a temporary plus an inner product per vector.
+int fold_linsolve(bk_ctx* ctx, bk_problem* prob, bk_op* J, const double* x, const double* params, int nparams, int ipar,
+                  const double* v, const double* w, int nrhs, const double* const* rhsu, const double* rhsp,
+                  const bk_gmres_opts& lo, bk_precond* pl, double* const* dX, double* dsig, int* cv, int* itlinear) {
+    const size_t n = prob->nloc;
+    double h[4], g[4];
+    BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
+    WsGuard ws(ctx);
+    double *dpF = nullptr, *x2 = nullptr;
+    BK_TRY(ws.get(n, &dpF));
+    BK_TRY(ws.get(n, &x2));
+    BK_TRY(pde_dparam(ctx, prob->desc.pde, ipar, n, 1.0, x, dpF));           // analytic dpF (:88-89)
+    GmresResult r0, r1, r2;
+    BK_TRY(linsolve2(ctx, J, rhsu[0], dX[0], dpF, x2, 0.0, 1.0, lo, pl, &r0, &r2));
+    int c = r0.converged & r2.converged, its = r0.niter + r2.niter;
+    if (nrhs == 2) {
+        BK_TRY(linsolve(ctx, J, rhsu[1], dX[1], 0.0, 1.0, lo, pl, &r1));
+        c &= r1.converged;
+        its += r1.niter;
+    }
+    const double* X[3] = {dX[0], nrhs == 2 ? dX[1] : x2, x2};
+    double s[4];
+    BK_TRY(v_fold_contract(ctx, n, x, v, w, nrhs + 1, X, h, g, s));
+    const double sx2 = -s[nrhs], sp = -s[nrhs + 1];
+    for (int k = 0; k < nrhs; ++k) {
+        dsig[k] = (rhsp[k] - (-s[k])) / (sp - sx2);
+        BK_TRY(v_axpby(ctx, n, -dsig[k], x2, 1.0, dX[k]));
+    }
+    *cv = c;
+    *itlinear = its;
+    return 0;
+}
+
+// callback(state; fromNewton) as solver.hip's newton_cb: the built-in cbMaxNorm veto first, then the user's function
+int fold_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear, double p) {
+    if (no->max_residual > 0.0 && !(residual < no->max_residual)) return 0;
+    if (no->callback) return no->callback(no->callback_user, x, fx, residual, step, itlinear, p, nullptr, NAN, 1) != 0;
+    return 1;
+}
+
+int check_common(bk_ctx* ctx, bk_problem* prob) {
+    if (prob->ctx != ctx) return set_error(ctx, "fold: the problem belongs to another context");
+    return 0;
+}
+
+}  // namespace
+}  // namespace bk
+
+using namespace bk;
+
+extern "C" {
+
+int bk_d2f(bk_problem* prob, const double* u, const double* params, int nparams, const double* dx1, const double* dx2,
+           double* out) {
+    if (!prob || !u || !params || !dx1 || !dx2 || !out) return -1;
+    double h[4], g[4];
+    BK_TRY(fold_polys(prob, params, nparams, 0, h, g));
+    return v_fold_pw(prob->ctx, prob->nloc, u, h, dx1, dx2, out);
+}
+
+int bk_djdp(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* dx, double* out) {
+    if (!prob || !u || !params || !dx || !out) return -1;
+    double h[4], g[4];
+    BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
+    return v_fold_pw(prob->ctx, prob->nloc, u, g, dx, nullptr, out);
+}
+
+int bk_fold_contract(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* v,
+                     const double* w, int m, const double* const* X, double* out) {
+    if (!prob || !u || !params || !v || !w || !out || (m > 0 && !X)) return -1;
+    double h[4], g[4];
+    BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
+    if (m < 0 || m > 3) return set_error(prob->ctx, "bk_fold_contract: 0 <= m <= 3 (got %d)", m);
+    for (int k = 0; k < m; ++k)
+        if (!X[k]) return -1;
+    double s[4];
+    BK_TRY(v_fold_contract(prob->ctx, prob->nloc, u, v, w, m, X, h, g, s));
+    for (int k = 0; k < m; ++k) out[k] = s[k];
+    out[m] = -s[m];
+    return 0;
+}
+
+int bk_fold_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar,
+                  const double* a, const double* b, const bk_bordering_opts* bopts, const bk_gmres_opts* lsopts,
+                  bk_precond* pl, double* v, double* w, double* sigma, double* sigma_p, int* converged, int itlinear[2]) {
+    if (!ctx || !prob || !x || !params || !a || !b || !bopts || !lsopts || !v || !w || !sigma) return -1;
+    BK_TRY(check_common(ctx, prob));
+    double h[4], g[4];
+    BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
+    if (v == a || v == b || w == a || w == b) return set_error(ctx, "bk_fold_terms: v and w must not alias a or b");
+    if (v == w && a != b) return set_error(ctx, "bk_fold_terms: v == w needs a == b");
+    const size_t n = prob->nloc;
+    WsGuard ws(ctx);
+    double* zero = nullptr;
+    BK_TRY(ws.get(n, &zero));
+    bk_op* J = nullptr;
+    BK_TRY(bk_jacobian(prob, x, params, nparams, &J));
+    int cv = 0, it[2] = {0, 0};
+    int s = fold_terms(ctx, J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it);
+    bk_op_destroy(J);
+    BK_TRY(s);
+    if (sigma_p) {
+        double t[1];
+        BK_TRY(v_fold_contract(ctx, n, x, v, w, 0, nullptr, h, g, t));
+        *sigma_p = -t[0];
+    }
+    if (converged) *converged = cv;
+    if (itlinear) { itlinear[0] = it[0]; itlinear[1] = it[1]; }
+    return 0;
+}
+
+int bk_fold_linsolve(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar,
+                     const double* v, const double* w, int nrhs, const double* const* rhsu, const double* rhsp,
+                     const bk_gmres_opts* lsopts, bk_precond* pl, double* const* dX, double* dsigma, int* converged,
+                     int* itlinear) {
+    if (!ctx || !prob || !x || !params || !v || !w || !rhsu || !rhsp || !lsopts || !dX || !dsigma) return -1;
+    BK_TRY(check_common(ctx, prob));
+    if (nrhs < 1 || nrhs > 2) return set_error(ctx, "bk_fold_linsolve: 1 or 2 right-hand sides (got %d)", nrhs);
+    for (int k = 0; k < nrhs; ++k) {
+        if (!rhsu[k] || !dX[k]) return -1;
+        for (int j = 0; j < nrhs; ++j)
+            if (dX[k] == rhsu[j]) return set_error(ctx, "bk_fold_linsolve: dX must not alias a right-hand side");
+    }
+    if (nrhs == 2 && dX[0] == dX[1]) return set_error(ctx, "bk_fold_linsolve: dX[0] and dX[1] must be distinct");
+    bk_op* J = nullptr;
+    BK_TRY(bk_jacobian(prob, x, params, nparams, &J));
+    int cv = 0, it = 0;
+    int s = fold_linsolve(ctx, prob, J, x, params, nparams, ipar, v, w, nrhs, rhsu, rhsp, *lsopts, pl, dX, dsigma, &cv, &it);
+    bk_op_destroy(J);
+    BK_TRY(s);
+    if (converged) *converged = cv;
+    if (itlinear) *itlinear = it;
+    return 0;
+}
+
+int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const double* params, int nparams, int ipar,
+                   const double* a, const double* b, const bk_newton_opts* no, const bk_bordering_opts* bopts,
+                   const bk_gmres_opts* lsopts, bk_precond* pl, double* v, double* w, double* sigma, bk_newton_result* res) {
+    if (!ctx || !prob || !x || !p || !params || !a || !b || !no || !bopts || !lsopts || !v || !w || !sigma || !res) return -1;
+    BK_TRY(check_common(ctx, prob));
+    if (no->max_iterations > BK_MAX_NEWTON_ITER) return set_error(ctx, "max_iterations > %d", BK_MAX_NEWTON_ITER);
+    double h[4], g[4];
+    BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
+    if (x == a || x == b || v == a || v == b || w == a || w == b || v == x || w == x)
+        return set_error(ctx, "bk_newton_fold: x, v and w must be distinct from a and b and from each other");
+    if (v == w && a != b) return set_error(ctx, "bk_newton_fold: v == w needs a == b");
+    const size_t n = prob->nloc;
+    const bool inf = no->norm_inf != 0;
+    WsGuard ws(ctx);
+    double *fx = nullptr, *dX = nullptr, *zero = nullptr;
+    BK_TRY(ws.get(n, &fx));
+    BK_TRY(ws.get(n, &dX));
+    BK_TRY(ws.get(n, &zero));
+    double par[BK_MAX_PARAMS];
+    for (int i = 0; i < nparams; ++i) par[i] = params[i];
+    double pc = *p;
+    int itlin = 0;
+    // one evaluation of the fold residual (:16-38) at (x, pc): F, and sigma with the bordered vectors v, w of this point, which
+    // the Newton step at the same point reuses (the reference solves them again in _get_bordered_terms, :71-99)
+    auto point = [&](double* r) -> int {
+        par[ipar] = pc;
+        bk_op* J = nullptr;
+        BK_TRY(bk_jacobian(prob, x, par, nparams, &J));
+        int cv = 0, it[2] = {0, 0};
+        int s = fold_terms(ctx, J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it);
+        bk_op_destroy(J);
+        BK_TRY(s);
+        itlin += it[0] + it[1];
+        if (!cv) ctx->diag.fold_unconverged += 1.0;
+        BK_TRY(bk_residual(prob, x, par, nparams, fx));
+        return norm_fold(ctx, n, fx, *sigma, inf, r);
+    };
+    double r;
+    BK_TRY(point(&r));
+    int step = 0;
+    res->residuals[0] = r;
+    int compute = fold_cb(no, x, fx, r, 0, 0, pc);
+    while (step < no->max_iterations && r > no->tol && compute) {
+        // Newton step: J_fold [dX; dsig] = [F; sigma] with foldMALinearSolver (:119-166), x -= dX, p -= dsig (src/Newton.jl:97)
+        par[ipar] = pc;
+        bk_op* J = nullptr;
+        BK_TRY(bk_jacobian(prob, x, par, nparams, &J));
+        const double* rhsu[1] = {fx};
+        double* dXs[1] = {dX};
+        double rhsp[1] = {*sigma}, dsig[1] = {0.0};
+        int cv = 0, it = 0;
+        int s = fold_linsolve(ctx, prob, J, x, par, nparams, ipar, v, w, 1, rhsu, rhsp, *lsopts, pl, dXs, dsig, &cv, &it);
+        bk_op_destroy(J);
+        BK_TRY(s);
+        itlin += it;
+        if (!cv) ctx->diag.fold_unconverged += 1.0;
+        BK_TRY(v_axpby(ctx, n, -1.0, dX, 1.0, x));
+        pc -= dsig[0];
+        const int before = itlin;
+        BK_TRY(point(&r));
+        step += 1;
+        res->residuals[step] = r;
+        compute = fold_cb(no, x, fx, r, step, it + (itlin - before), pc);
+    }
+    *p = pc;
+    res->converged = (res->residuals[step] < no->tol) & fold_cb(no, x, fx, r, step, 0, pc);
+    res->itnewton = step;
+    res->itlinear = itlin;
+    return 0;
+}
+
+}  // extern "C"

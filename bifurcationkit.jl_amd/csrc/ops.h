@@ -258,5 +258,9 @@ int linsolve(bk_ctx* ctx, bk_op* J, const double* rhs, double* x, double a0, dou
 // two independent solves with the same operator, concurrently on two lanes where supported (solver.hip)
 int linsolve2(bk_ctx* ctx, bk_op* J, const double* rhs1, double* x1, const double* rhs2, double* x2, double a0, double a1,
               const bk_gmres_opts& o, bk_precond* pl, GmresResult* r1, GmresResult* r2);
+// BorderingBLS (src/LinearBorderSolver.jl:88-166) on an unbordered operator (solver.hip; bk_bls_bordering without the checks)
+int bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R, double nn,
+                  double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_bordering_opts& bo,
+                  const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2]);
 
 }  // namespace bk

@@ -464,6 +464,54 @@ int bk_newton_deflated(bk_ctx* ctx, bk_problem* prob, double* x, const double* p
                        int accumulator_mean, double delta, const bk_newton_opts* nopts,
                        const bk_gmres_opts* lsopts, bk_precond* pl, bk_newton_result* res);
 
+/* ------------------------------------------------------------------ fold points (codim 2) ---------------
+ * The minimally augmented fold formulation of src/codim2/MinAugFold.jl, matrix-free (the reference assembles it for MatrixBLS /
+ * MinAugMatrixBased): unknowns (x, p = params[ipar]), G(x, p) = (F(x, p), sigma(x, p)) with sigma from
+ * [J a; b' 0][v; sigma] = [0; 1] and the adjoint system [J' b; a' 0][w; sigma2] = [0; 1].  Defined for BK_PDE_SH (2-D / 3-D)
+ * and BK_PDE_SH1D, whose Jacobians are symmetric (J' = J, :79-84) and whose Hessians are pointwise; any other problem returns
+ * an error.  The Newton solve is only as good as the linear solver on the near-singular J: it is demonstrated for SH with the
+ * spectral preconditioner; SH1D has no preconditioner here, and unpreconditioned GMRES does not converge on its J (N = 200).
+ * Vectors have the problem's local length (ranks: z-slabs); the scalars come from the all-reduced reductions of the BLAS-1 and
+ * contraction kernels (not yet exercised on more than one rank).                                                           */
+/* out = d2F(u, params)[dx1, dx2] (src/Problems.jl:107,165): SH (2 nu - 6 u) dx1 dx2 (examples/SH2d-fronts.jl:40), SH1D
+ * (6 nu u - 20 u^3) dx1 dx2 (examples/SHpde_snaking.jl:26); pointwise, no halo.                                       */
+int bk_d2f(bk_problem* prob, const double* u, const double* params, int nparams, const double* dx1, const double* dx2,
+           double* out);
+/* out = dJ/dp(u) dx for params[ipar]: J depends on the parameter only through the pointwise term, factor SH l: 1, nu: 2u;
+ * SH1D lambda: 1, nu: 3u^2 -- the analytic value of the central difference dJvdp of _get_bordered_terms (MinAugFold.jl:93-94). */
+int bk_djdp(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* dx, double* out);
+/* One streaming pass over u, v, w and m <= 3 device vectors X[k]:  out[k] = <w, d2F(u)[v, X_k]>  (k < m),
+ * out[m] = -<w, dJ/dp(u) v> = sigma_p for params[ipar]  (the inner products of foldMALinearSolver, MinAugFold.jl:153-157,
+ * and of _get_bordered_terms, :95).  Host out[m + 1]; deterministic, all-reduced.                                    */
+int bk_fold_contract(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* v,
+                     const double* w, int m, const double* const* X, double* out);
+/* _compute_bordered_vectors + the sigma_p of _get_bordered_terms (MinAugFold.jl:54-99) at (x, params): v and sigma from the
+ * BorderingBLS solve bls(J, a, b, 0, 0, 1) (bopts / lsopts / pl as bk_bls_bordering), w from bls(J', b, a, 0, 0, 1) -- or
+ * w = v with no second solve when a and b are the SAME pointer (newton_fold(br, ind) passes one vector twice, :246-247).
+ * sigma_p (may be NULL) = -<w, dJ/dp v> for params[ipar].  itlinear[0] / [1]: GMRES counts of the v / w solves.        */
+int bk_fold_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar,
+                  const double* a, const double* b, const bk_bordering_opts* bopts, const bk_gmres_opts* lsopts,
+                  bk_precond* pl, double* v, double* w, double* sigma, double* sigma_p, int* converged, int itlinear[2]);
+/* foldMALinearSolver, usehessian branch (MinAugFold.jl:119-166) for nrhs = 1 or 2 right-hand sides (rhsu[k] device, rhsp[k]
+ * host) at (x, params) with the bordered vectors v, w of that point: x1_k = J \ rhsu_k, ONE x2 = J \ dpF shared by all
+ * right-hand sides (dpF analytic), dsigma_k = (rhsp_k - sx1_k) / (sigma_p - sx2) with sx = -<w, d2F[., v]> from one fused pass,
+ * dX_k = x1_k - dsigma_k x2.  nrhs + 1 GMRES solves (the reference: 2 nrhs).  *itlinear = their GMRES counts.             */
+int bk_fold_linsolve(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar,
+                     const double* v, const double* w, int nrhs, const double* const* rhsu, const double* rhsp,
+                     const bk_gmres_opts* lsopts, bk_precond* pl, double* const* dX, double* dsigma, int* converged,
+                     int* itlinear);
+/* newton_fold (MinAugFold.jl:211-233) under the semantics of _newton (src/Newton.jl:66-114): (x, *p) = guess on entry, fold
+ * point on exit; tol applies to |(F, sigma)| in the chosen norm (norm_inf: max(|F|_inf, |sigma|), else the 2-norm of the
+ * BorderedArray); callback as bk_newton (p = the fold parameter, z0u = NULL).  Each point's v and w are solved ONCE and serve
+ * both its residual sigma and the Newton step taken from it (the reference solves them again for the Jacobian).  On exit
+ * v, w, *sigma are those of the returned point; res->itlinear = every GMRES count run (bordered vectors and steps).
+ * As in _newton the linear solves' convergence flags do not enter res->converged; each unconverged bordered-vector or step
+ * solve adds 1 to the context counter "fold_unconverged_solves" (bk_ctx_get_option; reset with bk_ctx_set_option(.., 0)). */
+int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const double* params, int nparams, int ipar,
+                   const double* a, const double* b, const bk_newton_opts* nopts, const bk_bordering_opts* bopts,
+                   const bk_gmres_opts* lsopts, bk_precond* pl, double* v, double* w, double* sigma,
+                   bk_newton_result* res);
+
 #ifdef __cplusplus
 }
 #endif
