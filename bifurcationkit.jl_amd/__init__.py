@@ -5,7 +5,7 @@ Only what the hot path needs:
   _lib.py    ctypes binding of the C ABI (the Python twin of julia/BifurcationKitHIP.jl)
   hip.py     mirror of the reference's plugin surface (linear / bordered / eigen solvers, problems)
   continuation.py   minimal restatement of the caller (newton, newton_palc, PALC loop) for parity tests
-  codim2.py  fold points: minimally augmented refinement (newton_fold) and fold-curve continuation
+  codim2.py  fold and Hopf points: minimally augmented refinement (newton_fold, newton_hopf) and codim-2 curve continuation
 
 Import name: ``bk_amd`` (the directory name is not a valid Python identifier; ``bk_amd.py`` at the repo
 root registers this package under that name).

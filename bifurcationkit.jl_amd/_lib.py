@@ -187,6 +187,15 @@ SIGNATURES = {
                              C.POINTER(VP), c_double_p, c_int_p, c_int_p]),
     "bk_newton_fold": (I, [VP, VP, VP, c_double_p, c_double_p, I, I, VP, VP, C.POINTER(NewtonOpts), C.POINTER(BorderingOpts),
                            C.POINTER(GmresOpts), VP, VP, VP, c_double_p, C.POINTER(NewtonResult)]),
+    "bk_hopf_d2f": (I, [VP, VP, c_double_p, I, VP, VP, VP]),
+    "bk_hopf_djdp": (I, [VP, VP, c_double_p, I, I, VP, VP]),
+    "bk_hopf_contract": (I, [VP, VP, c_double_p, I, I, VP, VP, VP, VP, I, C.POINTER(VP), c_double_p]),
+    "bk_hopf_terms": (I, [VP, VP, VP, c_double_p, I, I, D, VP, VP, VP, VP, C.POINTER(GmresOpts), VP, VP, VP, VP, VP,
+                          c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]),
+    "bk_hopf_linsolve": (I, [VP, VP, VP, c_double_p, I, I, VP, VP, VP, VP, I, C.POINTER(VP), c_double_p, C.POINTER(GmresOpts),
+                             VP, C.POINTER(VP), c_double_p, c_int_p, c_int_p]),
+    "bk_newton_hopf": (I, [VP, VP, VP, c_double_p, c_double_p, c_double_p, I, I, VP, VP, VP, VP, C.POINTER(NewtonOpts),
+                           C.POINTER(GmresOpts), VP, VP, VP, VP, VP, c_double_p, C.POINTER(NewtonResult)]),
 }
 
 _lib = None

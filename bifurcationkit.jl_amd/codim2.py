@@ -1,6 +1,6 @@
-"""Fold points: refinement and two-parameter continuation with the minimally augmented formulation of
-src/codim2/MinAugFold.jl, matrix-free on the preconditioned GMRES path (the reference assembles the system for MatrixBLS /
-MinAugMatrixBased, which cannot run at the sizes of this library).
+"""Fold and Hopf points: refinement and two-parameter continuation with the minimally augmented formulations of
+src/codim2/MinAugFold.jl and MinAugHopf.jl (Hopf: the second half of this module), matrix-free on the preconditioned GMRES
+path (the reference assembles the systems for MatrixBLS / MinAugMatrixBased, which cannot run at the sizes of this library).
 
   FoldProblem              FoldMinimallyAugmentedFormulation + FoldMAProblem: G(X, p2) = (F(x, p1), sigma(x, p1)), X = (x, p1)
   FoldLinearSolverMinAug   foldMALinearSolver, usehessian branch (:119-166): one or two right-hand sides, one shared J \\ dpF
@@ -403,6 +403,454 @@ def continuation_fold(prob, fold_guess: BorderedArray, p2: float, lens2: str, a:
             tau = Cn.secant_tangent(z, z_old, ds_next, theta)
             bt = F.update(z.u, z.p) if Cn.mod_counter(step, update_minaug_every_step) else float("nan")
             record(z, sol, ds, bt, tau.p)
+        ds = ds_next
+        if stop:
+            break
+        z_pred = z.copy().add_(tau, ds)
+    return br
+
+
+# ================================================================================================== Hopf points
+# The minimally augmented Hopf formulation of src/codim2/MinAugHopf.jl, matrix-free, for CGL2d (the one problem here whose
+# Jacobian is not symmetric):
+#
+#   HopfVec                  the unknown X = (x, [p1, omega]); BorderedArray holds a scalar p only
+#   HopfProblem              HopfMinimallyAugmentedFormulation + HopfMAProblem: G(X, p2) = (F(x, p1), Re sigma, Im sigma)
+#   HopfLinearSolverMinAug   _hopf_MA_linear_solver, usehessian branch: one or two right-hand sides, one shared J \ dpF
+#   hopf_point               hopf_point(br, ind) on a native branch record (save_sol = True)
+#   hopf_start_vectors       the reference's default start vectors (random a, b, then the bordered vectors) or, with an
+#                            eigensolver, start_with_eigen (zeta from the eigensolver, zeta* from the adjoint bordered solve)
+#   newton_hopf              newton_hopf written out call by call (BorderingBLS.solve_complex, bk_gmres2, hopf_contract)
+#   newton_hopf_native       the same as one library call (bk_newton_hopf)
+#   continuation_hopf        PALC on G(X, p2), Secant tangent, BorderingBLS(HopfLinearSolverMinAug, check_precision = false),
+#                            a / b updated after every step, stop at |omega| < 100 tol (threshBT of update!)
+#
+# Complex device vectors are (re, im) pairs of HipVecs.  With w^H a = 1:  sigma_x . dx = -w^H d2F[v, dx],
+# sigma_p = -w^H dJ/dp v, sigma_omega = i w^H v.
+class HopfVec:
+    """(u, p) with p = [p1, omega]: the VectorInterface subset PALC and the bordered solvers use."""
+    __slots__ = ("u", "p")
+
+    def __init__(self, u, p):
+        self.u = u
+        self.p = np.array(p, dtype=np.float64).reshape(2)
+
+    def copy(self):
+        return HopfVec(self.u.copy(), self.p.copy())
+
+    def zerovector(self):
+        return HopfVec(self.u.zerovector(), np.zeros(2))
+
+    def copyto_(self, src):
+        self.u.copyto_(src.u)
+        self.p[:] = src.p
+        return self
+
+    def scale_(self, a):
+        self.u.scale_(a)
+        self.p *= a
+        return self
+
+    def add_(self, x, a=1.0, b=1.0):
+        self.u.add_(x.u, a, b)
+        self.p = b * self.p + a * x.p
+        return self
+
+    def inner(self, y):
+        return self.u.inner(y.u) + float(self.p @ y.p)
+
+    def norm(self):
+        return math.sqrt(self.u.norm() ** 2 + float(self.p @ self.p))
+
+    def norminf(self):
+        return _nanmax(self.u.norminf(), *np.abs(self.p))
+
+    def __len__(self):
+        return len(self.u) + 2
+
+
+def _nanmax(*vals):
+    """max that propagates a NaN from any argument (Python's max drops it depending on the argument order)."""
+    vals = [float(v) for v in vals]
+    return math.nan if any(v != v for v in vals) else max(vals)
+
+
+def _cptr(z):
+    return _ptr(z.t) if z is not None else None
+
+
+def cnorm(z):
+    """|z| of a complex (re, im) pair."""
+    re, im = z
+    return math.sqrt(re.norm() ** 2 + (im.norm() ** 2 if im is not None else 0.0))
+
+
+def cinner(x, y):
+    """x^H y of (re, im) pairs (VI.inner on complex vectors)."""
+    (xr, xi), (yr, yi) = x, y
+    re = xr.inner(yr) + (xi.inner(yi) if xi is not None and yi is not None else 0.0)
+    im = (xr.inner(yi) if yi is not None else 0.0) - (xi.inner(yr) if xi is not None else 0.0)
+    return complex(re, im)
+
+
+def _cscale(z, c: complex):
+    """c z for a complex pair, as a new pair."""
+    re, im = z
+    im = im if im is not None else re.zerovector()
+    return (re.copy().scale_(c.real).add_(im, -c.imag), im.copy().scale_(c.real).add_(re, c.imag))
+
+
+def hopf_d2F(prob, x: HipVec, pars, dx1: HipVec, dx2: HipVec) -> HipVec:
+    """d2F(x)[dx1, dx2] of CGL2d for real dx1, dx2 (bk_hopf_d2f)."""
+    ctx, out = prob.ctx, x.similar()
+    arr = (C.c_double * len(pars))(*pars)
+    ctx.check(ctx.lib.bk_hopf_d2f(prob.h, _ptr(x.t), arr, len(pars), _ptr(dx1.t), _ptr(dx2.t), _ptr(out.t)), "bk_hopf_d2f")
+    return out
+
+
+def hopf_dJdp(prob, x: HipVec, pars, ipar: int, dx: HipVec) -> HipVec:
+    """dJ/dp(x) dx of CGL2d for params[ipar] (bk_hopf_djdp)."""
+    ctx, out = prob.ctx, x.similar()
+    arr = (C.c_double * len(pars))(*pars)
+    ctx.check(ctx.lib.bk_hopf_djdp(prob.h, _ptr(x.t), arr, len(pars), int(ipar), _ptr(dx.t), _ptr(out.t)), "bk_hopf_djdp")
+    return out
+
+
+def hopf_contract(prob, x: HipVec, pars, ipar: int, v, w, X=()):
+    """One fused pass (bk_hopf_contract): ([w^H d2F(x)[v, X_k] for X_k in X], w^H dJ/dp v, w^H v) as complex numbers."""
+    ctx = prob.ctx
+    m = len(X)
+    arr = (C.c_double * len(pars))(*pars)
+    xp = (C.c_void_p * max(m, 1))(*[t.t.data_ptr() for t in X])
+    out = (C.c_double * (2 * (m + 2)))()
+    ctx.check(ctx.lib.bk_hopf_contract(prob.h, _ptr(x.t), arr, len(pars), int(ipar), _ptr(v[0].t), _ptr(v[1].t), _ptr(w[0].t),
+                                       _ptr(w[1].t), m, xp, out), "bk_hopf_contract")
+    z = [complex(out[2 * k], out[2 * k + 1]) for k in range(m + 2)]
+    return z[:m], z[m], z[m + 1]
+
+
+def hopf_terms(prob, x: HipVec, pars, ipar: int, omega: float, a, b, ls: _GMRES):
+    """bk_hopf_terms: (v, w, sigma, sigma_p, sigma_omega, converged, (itv, itw)); v, w as (re, im) pairs."""
+    ctx = prob.ctx
+    arr = (C.c_double * len(pars))(*pars)
+    vr, vi, wr, wi = x.similar(), x.similar(), x.similar(), x.similar()
+    sg, spp, sw = (C.c_double * 2)(), (C.c_double * 2)(), (C.c_double * 2)()
+    cv = C.c_int()
+    it = (C.c_int * 2)()
+    lo = ls._opts()
+    ctx.check(ctx.lib.bk_hopf_terms(ctx.h, prob.h, _ptr(x.t), arr, len(pars), int(ipar), float(omega), _cptr(a[0]), _cptr(a[1]),
+                                    _cptr(b[0]), _cptr(b[1]), C.byref(lo), ls._pl(), _ptr(vr.t), _ptr(vi.t), _ptr(wr.t),
+                                    _ptr(wi.t), sg, spp, sw, C.byref(cv), it), "bk_hopf_terms")
+    return ((vr, vi), (wr, wi), complex(sg[0], sg[1]), complex(spp[0], spp[1]), complex(sw[0], sw[1]), bool(cv.value),
+            (it[0], it[1]))
+
+
+def _hopf_2x2(S1: complex, S2: complex, P: complex, Q: complex, rp: float, rw: float):
+    """(dp, domega) of (sigma_p + S2) dp + sigma_omega domega = (rp + i rw) + S1 with sigma_p = -P, sigma_omega = i Q: the same
+    2 x 2 real system and operation order as bk_hopf_linsolve."""
+    spr, spi = -P.real, -P.imag
+    swr, swi = -Q.imag, Q.real
+    a11, a12, a21, a22 = spr + S2.real, swr, spi + S2.imag, swi
+    det = a11 * a22 - a12 * a21
+    b1, b2 = rp + S1.real, rw + S1.imag
+    return (b1 * a22 - a12 * b2) / det, (a11 * b2 - a21 * b1) / det
+
+
+def _norm_hopf(F, sigma: complex, norm_inf):
+    if norm_inf:
+        return _nanmax(F.norminf(), abs(sigma.real), abs(sigma.imag))
+    return math.sqrt(F.norm() ** 2 + sigma.real ** 2 + sigma.imag ** 2)
+
+
+# ------------------------------------------------------------------------------------------ Hopf point guesses
+def hopf_point(br, ind: int) -> HopfVec:
+    """hopf_point(br, index) (MinAugHopf.jl:6-13) on a branch of continuation.continuation_native(..., bisection = True,
+    save_sol = True): x = the saved (bisected) state of the special point, p its parameter, omega = |Im lambda| of the pair that
+    crossed, i.e. of the eigenvalue with non-zero imaginary part nearest the imaginary axis in br.eig of that point."""
+    sp = br.specialpoint[ind]
+    if sp.get("type") != "hopf":
+        raise ValueError("The provided index does not refer to a Hopf point")
+    i = sp["step"]
+    x, p = _saved(br, i)
+    vals = np.asarray(br.eig[i])
+    cand = vals[np.abs(vals.imag) > 0]
+    if cand.size == 0:
+        raise ValueError("no complex eigenvalue recorded at the Hopf point")
+    lam = cand[np.argmin(np.abs(cand.real))]
+    return HopfVec(x.copy(), [float(sp["param"]), abs(float(lam.imag))])
+
+
+def hopf_start_vectors(prob, X: HopfVec, ls: _GMRES, eig=None, nev=4, seed=0):
+    """(a, b) for newton_hopf / continuation_hopf at the guess X.  Default (continuation_hopf, :566-585): random complex a, b, then
+    the bordered vectors of the guess, a = w/|w|, b = v/|v|.  With an eigensolver (start_with_eigen): b = zeta, the eigenvector
+    of J(x, p) whose eigenvalue lambda is nearest i omega (``save_vectors``), a = zeta* from the adjoint bordered solve, scaled so
+    that a^H b = 1.  The eigensolver keeps one (re, im) pair per conjugate pair; which member it describes is checked on J itself:
+    J zr = Re(lambda) zr - Im(lambda) zi holds for the eigenvector of lambda, J zr = Re(lambda) zr + Im(lambda) zi for its
+    conjugate, whose imaginary part is then negated."""
+    x, (p, omega) = X.u, X.p
+    pv = prob._pvec(p)
+    if eig is None:
+        rng = np.random.default_rng(seed)
+        n = x.n
+        a = tuple(HipVec.from_numpy(prob.ctx, rng.random(n), x.nglobal) for _ in range(2))
+        b = tuple(HipVec.from_numpy(prob.ctx, rng.random(n), x.nglobal) for _ in range(2))
+        v, w, *_ = hopf_terms(prob, x, pv, prob.ipar, omega, a, b, ls)
+        return _cscale(w, 1.0 / cnorm(w)), _cscale(v, 1.0 / cnorm(v))
+    J = prob.jacobian(x, p)
+    vals, vecs, _, _ = eig(J, nev)
+    if vecs is None:
+        raise ValueError("start_with_eigen needs the eigenvectors (an eigensolver with save_vectors = True)")
+    k = int(np.argmin(np.abs(np.asarray(vals) - 1j * omega)))
+    lam = complex(vals[k])
+    zr, zi = vecs[k]
+    zeta = (zr.copy(), zi.copy() if zi is not None else zr.zerovector())
+    Jzr = J(zeta[0])
+    own = Jzr.copy().add_(zeta[0], -lam.real).add_(zeta[1], lam.imag).norm()          # J zr - (Re l zr - Im l zi)
+    conj = Jzr.add_(zeta[0], -lam.real).add_(zeta[1], -lam.imag).norm()               # J zr - (Re l zr + Im l zi)
+    if conj < own:
+        zeta[1].scale_(-1.0)
+    zeta = _cscale(zeta, 1.0 / cnorm(zeta))
+    _, w, *_ = hopf_terms(prob, x, pv, prob.ipar, omega, zeta, zeta, ls)
+    c = cinner(w, zeta)
+    return _cscale(w, 1.0 / c.conjugate()), zeta
+
+
+# ------------------------------------------------------------------------------------------ newton_hopf
+def newton_hopf(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=25, norm_inf=False):
+    """newton_hopf with HopfLinearSolverMinAug under _newton (src/Newton.jl:66-114), call by call on the plugin surface: the
+    residual solves bls(J, a, b, 0, 0, 1; shift = -i omega) for (v, sigma) and bls(J', b, a, 0, 0, 1; shift = +i omega) for w
+    (BorderingBLS.solve_complex); each Newton step is _hopf_MA_linear_solver's usehessian branch with ls(J, F, dpF) (bk_gmres2)
+    and one hopf_contract pass for S(x1), S(x2), w^H dJ/dp v and w^H v.  v, w of a point serve its residual and its step."""
+    bls = BorderingBLS(ls, check_precision=False)
+    ipar = prob.ipar
+    x, p, om = X0.u.copy(), float(X0.p[0]), float(X0.p[1])
+    itlin, bad = 0, 0
+
+    def point():
+        nonlocal itlin, bad
+        J, Jt = prob.jacobian(x, p), prob.jacobian_adjoint(x, p)
+        zero = x.zerovector()
+        v, sigma, cv, itv = bls.solve_complex(J, a, b, 0.0, (zero, None), 1.0, shift=complex(0.0, -om))
+        w, _, cv2, itw = bls.solve_complex(Jt, b, a, 0.0, (zero, None), 1.0, shift=complex(0.0, om))
+        itlin += int(np.sum(itv)) + int(np.sum(itw))
+        bad += 0 if (cv and cv2) else 1
+        return prob.residual(x, p), sigma, v, w
+
+    F, sigma, v, w = point()
+    res = [_norm_hopf(F, sigma, norm_inf)]
+    step = 0
+    while step < max_iterations and res[-1] > tol:
+        pars = prob._pvec(p)
+        J = prob.jacobian(x, p)
+        x1, x2, cv, it = _solve2(ls, J, F, dpF(prob, x, pars, ipar))
+        itlin += int(np.sum(it))
+        bad += 0 if cv else 1
+        (S1, S2), P, Q = hopf_contract(prob, x, pars, ipar, v, w, [x1, x2])
+        dp, dw = _hopf_2x2(S1, S2, P, Q, sigma.real, sigma.imag)
+        x1.add_(x2, -dp)
+        x.add_(x1, -1.0)
+        p -= dp
+        om -= dw
+        F, sigma, v, w = point()
+        res.append(_norm_hopf(F, sigma, norm_inf))
+        step += 1
+    return dict(u=HopfVec(x, [p, om]), converged=res[-1] < tol, itnewton=step, itlineartot=itlin, residuals=res, v=v, w=w,
+                sigma=sigma, unconverged_solves=bad)
+
+
+def newton_hopf_native(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=25, norm_inf=False, callback=None):
+    """The same as one library call (bk_newton_hopf)."""
+    ctx = prob.ctx
+    x = X0.u.copy()
+    p, om = C.c_double(float(X0.p[0])), C.c_double(float(X0.p[1]))
+    pv = prob._pvec(p.value)
+    arr = (C.c_double * len(pv))(*pv)
+    vr, vi, wr, wi = x.similar(), x.similar(), x.similar(), x.similar()
+    sigma = (C.c_double * 2)()
+    no = newton_opts(tol, max_iterations, norm_inf, callback=callback)
+    lo = ls._opts()
+    res = L.NewtonResult()
+    bad0 = ctx.get_option("hopf_unconverged_solves")
+    ctx.check(ctx.lib.bk_newton_hopf(ctx.h, prob.h, _ptr(x.t), C.byref(p), C.byref(om), arr, len(pv), prob.ipar, _cptr(a[0]),
+                                     _cptr(a[1]), _cptr(b[0]), _cptr(b[1]), C.byref(no), C.byref(lo), ls._pl(), _ptr(vr.t),
+                                     _ptr(vi.t), _ptr(wr.t), _ptr(wi.t), sigma, C.byref(res)), "bk_newton_hopf")
+    return dict(u=HopfVec(x, [p.value, om.value]), converged=bool(res.converged), itnewton=res.itnewton,
+                itlineartot=res.itlinear, residuals=[res.residuals[i] for i in range(res.itnewton + 1)], v=(vr, vi), w=(wr, wi),
+                sigma=complex(sigma[0], sigma[1]),
+                unconverged_solves=int(ctx.get_option("hopf_unconverged_solves") - bad0))
+
+
+# ------------------------------------------------------------------------------------------ the Hopf problem G(X, p2)
+class HopfProblem:
+    """HopfMinimallyAugmentedFormulation(prob, a, b, ...) + HopfMAProblem with lens2: unknown X = HopfVec(x, [p1, omega]),
+    parameter p2 = ``lens2``.  ``residual`` / ``jacobian`` / ``residual_dparam`` are the surface continuation.newton_palc
+    drives; the bordered vectors of a point are solved once per point (bk_hopf_terms)."""
+
+    def __init__(self, prob, lens2: str, a, b, ls: _GMRES):
+        if lens2 == prob.lens:
+            raise ValueError(f"Please choose 2 different parameters. You only passed {lens2}")
+        self.prob, self.ctx = prob, prob.ctx
+        self.lens1, self.lens2 = prob.lens, lens2
+        self.ipar1, self.ipar2 = prob.param_names.index(prob.lens), prob.param_names.index(lens2)
+        self.ls = ls
+        self.a, self.b = a, b
+        self.delta = prob.delta
+        self.itlinear = 0
+        self._cache = None
+
+    def pvec(self, p1, p2):
+        return _params(self.prob, **{self.lens1: p1, self.lens2: p2})
+
+    def terms(self, X: HopfVec, p2: float):
+        """(v, w, sigma) at (X, p2), solved once per point."""
+        c = self._cache
+        if c is not None and np.array_equal(c[1], X.p) and c[2] == p2 and torch.equal(c[0].t, X.u.t):
+            return c[3]
+        v, w, sigma, _, _, _, it = hopf_terms(self.prob, X.u, self.pvec(X.p[0], p2), self.ipar1, X.p[1], self.a, self.b, self.ls)
+        self.itlinear += it[0] + it[1]
+        t = (v, w, sigma)
+        self._cache = (X.u.copy(), X.p.copy(), p2, t)
+        return t
+
+    def residual(self, X: HopfVec, p2: float) -> HopfVec:
+        _, _, sigma = self.terms(X, p2)
+        return HopfVec(residual(self.prob, X.u, self.pvec(X.p[0], p2)), [sigma.real, sigma.imag])
+
+    def residual_dparam(self, X: HopfVec, p2: float, eps=None) -> HopfVec:
+        """dG/dp2 = (dF/dp2, sigma_p2) with sigma_p2 = -w^H dJ/dp2 v, analytic."""
+        v, w, _ = self.terms(X, p2)
+        pv = self.pvec(X.p[0], p2)
+        _, P, _ = hopf_contract(self.prob, X.u, pv, self.ipar2, v, w)
+        return HopfVec(dpF(self.prob, X.u, pv, self.ipar2), [-P.real, -P.imag])
+
+    def jacobian(self, X: HopfVec, p2: float):
+        return JacobianHopf(self, X, p2)
+
+    def update(self, X: HopfVec, p2: float):
+        """update!(probma, iter, state) after a converged step: a = w/|w|, b = v/|v| from the bordered vectors of the new
+        point; returns omega (BT test function: the curve is stopped when |omega| < threshBT)."""
+        v, w, _ = self.terms(X, p2)
+        self.a, self.b = _cscale(w, 1.0 / cnorm(w)), _cscale(v, 1.0 / cnorm(v))
+        self._cache = None
+        return float(X.p[1])
+
+
+@dataclass
+class JacobianHopf:
+    """What jacobian(HopfMAProblem, X, p2) hands to HopfLinearSolverMinAug: the point (no matrix)."""
+    hopf: HopfProblem
+    X: HopfVec
+    p2: float
+
+
+class HopfLinearSolverMinAug:
+    """HopfLinearSolverMinAug -> _hopf_MA_linear_solver, usehessian branch, as bk_hopf_linsolve.  ``solve2`` serves both
+    right-hand sides of the BorderingBLS BEC with ONE J \\ dpF solve: three real GMRES solves where the reference runs four."""
+
+    def _run(self, Jh: JacobianHopf, rhs):
+        H = Jh.hopf
+        v, w, _ = H.terms(Jh.X, Jh.p2)
+        ctx = H.ctx
+        pv = H.pvec(Jh.X.p[0], Jh.p2)
+        arr = (C.c_double * len(pv))(*pv)
+        m = len(rhs)
+        dX = [Jh.X.u.similar() for _ in range(m)]
+        ru = (C.c_void_p * m)(*[r.u.t.data_ptr() for r in rhs])
+        rp = (C.c_double * (2 * m))(*[float(c) for r in rhs for c in r.p])
+        dxp = (C.c_void_p * m)(*[d.t.data_ptr() for d in dX])
+        ds = (C.c_double * (2 * m))()
+        cv, it = C.c_int(), C.c_int()
+        lo = H.ls._opts()
+        ctx.check(ctx.lib.bk_hopf_linsolve(ctx.h, H.prob.h, _ptr(Jh.X.u.t), arr, len(pv), H.ipar1, _ptr(v[0].t), _ptr(v[1].t),
+                                           _ptr(w[0].t), _ptr(w[1].t), m, ru, rp, C.byref(lo), H.ls._pl(), dxp, ds,
+                                           C.byref(cv), C.byref(it)), "bk_hopf_linsolve")
+        return [HopfVec(dX[k], [ds[2 * k], ds[2 * k + 1]]) for k in range(m)], bool(cv.value), it.value
+
+    def __call__(self, Jh: JacobianHopf, rhs: HopfVec, a0=0.0, a1=1.0):
+        out, cv, it = self._run(Jh, [rhs])
+        return out[0], cv, it
+
+    def solve2(self, Jh: JacobianHopf, rhs1: HopfVec, rhs2: HopfVec, a0=0.0, a1=1.0):
+        out, cv, it = self._run(Jh, [rhs1, rhs2])
+        return out[0], out[1], cv, (it, 0)
+
+
+# ------------------------------------------------------------------------------------------ continuation_hopf
+@dataclass
+class HopfBranch:
+    """The record of continuation_hopf (record_from_solution): p1 (lens1), p2 (lens2), omega and BT = omega per point."""
+    p1: list = field(default_factory=list)
+    p2: list = field(default_factory=list)
+    omega: list = field(default_factory=list)
+    BT: list = field(default_factory=list)
+    ds: list = field(default_factory=list)
+    itnewton: list = field(default_factory=list)
+    itlinear: list = field(default_factory=list)
+    residuals: list = field(default_factory=list)
+    sol: list = field(default_factory=list)
+    stopped_at_bt: bool = False
+
+
+def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls: _GMRES, cp: Cn.ContinuationPar, theta=0.5,
+                      norm_inf=True, update_minaug_every_step=1, save_sol=False, ds_sequence=None, verbosity=0) -> HopfBranch:
+    """continuation_hopf(prob, alg = PALC(tangent = Secant()), hopfpointguess, par, lens1, lens2, a, b, options_cont) with
+    jacobian_ma = MinAug(): PALC on G(X, p2) through continuation.newton_palc with BorderingBLS(solver = HopfLinearSolverMinAug(),
+    check_precision = false), Secant tangent, the two starting points of continuation by newton on G, step-size control of
+    continuation.py.  After every converged step a, b are updated (update!) and the run stops once |omega| < 100 tol
+    (threshBT: the curve is near a Bogdanov-Takens point).  ``ds_sequence`` (optional) replaces the step-size control by a fixed
+    list of steps.  Codim-2 points are not located."""
+    H = HopfProblem(prob, lens2, a, b, ls)
+    lin = HopfLinearSolverMinAug()
+    nopt = Cn.NewtonPar(tol=cp.newton_options.tol, max_iterations=cp.newton_options.max_iterations, linsolver=lin)
+    bls = BorderingBLS(lin, check_precision=False)
+    normC = (lambda z: z.norminf()) if norm_inf else (lambda z: z.norm())
+    thresh_bt = 100 * cp.newton_options.tol
+    br = HopfBranch()
+    sol0 = Cn.newton(H, hopf_guess, p2, nopt, normC)
+    if not sol0.converged:
+        raise RuntimeError("Newton failed to converge for the initial Hopf guess")
+    ds = cp.ds if ds_sequence is None else ds_sequence[0]
+    p2b = p2 + ds / cp.eta
+    sol1 = Cn.newton(H, sol0.u, p2b, nopt, normC)
+    if not sol1.converged:
+        raise RuntimeError("Newton failed to converge. Required for the computation of the initial tangent")
+    z0, z1 = BorderedArray(sol0.u, p2), BorderedArray(sol1.u, p2b)
+
+    def record(z, sol, ds_, om):
+        br.p1.append(float(z.u.p[0])); br.p2.append(z.p); br.omega.append(float(z.u.p[1])); br.BT.append(om); br.ds.append(ds_)
+        br.itnewton.append(sol.itnewton); br.itlinear.append(sol.itlineartot); br.residuals.append(list(sol.residuals))
+        if save_sol:
+            br.sol.append(z.copy())
+
+    tau = Cn.secant_tangent(z1, z0, ds, theta)
+    z, z_old = z0.copy(), z0.copy()
+    record(z, sol0, ds, H.update(z.u, z.p))
+    z_pred = z.copy().add_(tau, ds)
+    step = 0
+    while step < cp.max_steps and (cp.p_min < z.p < cp.p_max or step == 0):
+        it0 = H.itlinear
+        sol = Cn.newton_palc(H, z, tau, z_pred, ds, theta, bls, nopt, cp.p_min, cp.p_max, normC)
+        sol.itlineartot += H.itlinear - it0
+        if verbosity:
+            print(f"hopf step {step:3d} ds={ds:+.3e} p2={sol.u.p:+.8f} p1={sol.u.u.p[0]:+.8f} omega={sol.u.u.p[1]:+.8f} "
+                  f"conv={sol.converged} itnewton={sol.itnewton} itlinear={sol.itlineartot}")
+        if sol.converged:
+            z_old.copyto_(z)
+            z.copyto_(sol.u)
+            step += 1
+        if ds_sequence is not None:
+            if not sol.converged:
+                raise RuntimeError(f"Hopf continuation step {step} did not converge with the prescribed ds")
+            ds_next, stop = (ds_sequence[step] if step < len(ds_sequence) else ds), step >= len(ds_sequence)
+        else:
+            ds_next, stop = Cn.step_size_control(ds, sol.converged, sol.itnewton, cp)
+        if sol.converged:
+            tau = Cn.secant_tangent(z, z_old, ds_next, theta)
+            om = H.update(z.u, z.p) if Cn.mod_counter(step, update_minaug_every_step) else float(z.u.p[1])
+            record(z, sol, ds, om)
+            if abs(om) < thresh_bt:
+                br.stopped_at_bt = True
+                break
         ds = ds_next
         if stop:
             break

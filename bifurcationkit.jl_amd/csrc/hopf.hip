@@ -1,0 +1,506 @@
+// Minimally augmented Hopf formulation, matrix-free: src/codim2/MinAugHopf.jl on the preconditioned GMRES path.
+//
+//   unknowns (x, p, omega), G(x, p, omega) = (F(x, p), Re sigma, Im sigma),
+//   [J - i omega, a; b^H, 0][v; sigma] = [0; 1],   [J' + i omega, b; a^H, 0][w; sigma2] = [0; 1]   (:17, :72-76)
+//
+// With w^H a = 1 the derivatives of sigma are  sigma_x . dx = -w^H d2F(x)[v, dx],  sigma_p = -w^H dJ/dp v,  sigma_omega = i w^H v.
+// Defined for BK_PDE_CGL2D, the one problem here whose Jacobian is not symmetric.  Its nonlinearity (examples/cGL2d.jl:24-40)
+//   NL(z) = (r + i nu) z - (c3 + i mu) |z|^2 z - c5 |z|^4 z + gamma,   z = u1 + i u2,
+// is pointwise and the Laplacian is linear, so d2F = d2NL: per grid point one symmetric 2 x 2 matrix H_f(u) for each field f,
+// d2F_f[a, b] = a^T H_f b.  H_f are the u-derivatives of the closed-form Jacobian of stencil.hip:cgl_kernel (f1u, f1v, f2u, f2v);
+// dJ/dp is the u-derivative of dparam_kernel's phi_p, a 2 x 2 matrix D_p(u) per point (zero for gamma).  Complex vectors are
+// (re, im) pairs of real device vectors; d2F and dJ/dp act on them by linearity.
+#include <cmath>
+
+#include "common.h"
+#include "ops.h"
+#include "stream.h"
+
+namespace bk {
+
+namespace {
+
+// ------------------------------------------------------------------ pointwise tensors
+struct CglCoef { double mu, c3, c5; int ipar; };
+
+// Hessian of NL at (u1, u2): H1 = [[h[0], h[1]], [h[1], h[2]]] (field 1), H2 = [[h[3], h[4]], [h[4], h[5]]] (field 2)
+__device__ __forceinline__ void cgl_hess(const CglCoef& c, double u1, double u2, double h[6]) {
+    const double ua = u1 * u1 + u2 * u2;
+    const double q1 = u1 * (8.0 * u1 * u1 + 12.0 * ua), q2 = u2 * (8.0 * u1 * u1 + 4.0 * ua);
+    const double q3 = u1 * (8.0 * u2 * u2 + 4.0 * ua), q4 = u2 * (8.0 * u2 * u2 + 12.0 * ua);
+    h[0] = -6.0 * c.c3 * u1 + 2.0 * c.mu * u2 - c.c5 * q1;
+    h[1] = -2.0 * c.c3 * u2 + 2.0 * c.mu * u1 - c.c5 * q2;
+    h[2] = -2.0 * c.c3 * u1 + 6.0 * c.mu * u2 - c.c5 * q3;
+    h[3] = -2.0 * c.c3 * u2 - 6.0 * c.mu * u1 - c.c5 * q2;
+    h[4] = -2.0 * c.c3 * u1 - 2.0 * c.mu * u2 - c.c5 * q3;
+    h[5] = -6.0 * c.c3 * u2 - 2.0 * c.mu * u1 - c.c5 * q4;
+}
+
+// dJ/dp at (u1, u2) for params[ipar] = (r, mu, nu, c3, c5, gamma): D = [[d[0], d[1]], [d[2], d[3]]]
+__device__ __forceinline__ void cgl_djdp(int ipar, double u1, double u2, double d[4]) {
+    const double ua = u1 * u1 + u2 * u2;
+    switch (ipar) {
+        case 0: d[0] = 1.0; d[1] = 0.0; d[2] = 0.0; d[3] = 1.0; break;
+        case 1: d[0] = 2.0 * u1 * u2; d[1] = 2.0 * u2 * u2 + ua; d[2] = -(2.0 * u1 * u1 + ua); d[3] = -2.0 * u1 * u2; break;
+        case 2: d[0] = 0.0; d[1] = -1.0; d[2] = 1.0; d[3] = 0.0; break;
+        case 3: d[0] = -(2.0 * u1 * u1 + ua); d[1] = -2.0 * u1 * u2; d[2] = d[1]; d[3] = -(2.0 * u2 * u2 + ua); break;
+        case 4: d[0] = -(4.0 * ua * u1 * u1 + ua * ua); d[1] = -4.0 * ua * u1 * u2; d[2] = d[1];
+                d[3] = -(4.0 * ua * u2 * u2 + ua * ua); break;
+        default: d[0] = d[1] = d[2] = d[3] = 0.0; break;
+    }
+}
+
+// ------------------------------------------------------------------ kernels
+// out = d2F(u)[x1, x2] (x2 != NULL) or dJ/dp(u) x1 (x2 == NULL) on the two stacked fields of N points each (bk_hopf_d2f,
+// bk_hopf_djdp)
+__global__ void __launch_bounds__(kThreads) hopf_pw_kernel(size_t N, const double* __restrict__ u, CglCoef c,
+                                                           const double* __restrict__ x1, const double* __restrict__ x2,
+                                                           double* __restrict__ out) {
+    const size_t stride = (size_t)gridDim.x * kThreads;
+    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < N; i += stride) {
+        const double u1 = u[i], u2 = u[i + N], a1 = x1[i], a2 = x1[i + N];
+        double o1, o2;
+        if (x2) {
+            double h[6];
+            cgl_hess(c, u1, u2, h);
+            const double b1 = x2[i], b2 = x2[i + N];
+            o1 = a1 * (h[0] * b1 + h[1] * b2) + a2 * (h[1] * b1 + h[2] * b2);
+            o2 = a1 * (h[3] * b1 + h[4] * b2) + a2 * (h[4] * b1 + h[5] * b2);
+        } else {
+            double d[4];
+            cgl_djdp(c.ipar, u1, u2, d);
+            o1 = d[0] * a1 + d[1] * a2;
+            o2 = d[2] * a1 + d[3] * a2;
+        }
+        out[i] = o1;
+        out[i + N] = o2;
+    }
+}
+
+// field-1 base pointers of the streams of hopf_contract_kernel; field 2 of each starts N doubles later
+struct HopfStreams { const double *u, *vr, *vi, *wr, *wi, *x[3]; };
+
+// One pass over u, v = (vr, vi), w = (wr, wi) and M real vectors X_k:
+//   S_k = w^H d2F(u)[v, X_k] (k < M),   P = w^H dJ/dp(u) v,   Q = w^H v,
+// 2 (M + 2) partial sums per workgroup in the order (Re S_0, Im S_0, ..., Re P, Im P, Re Q, Im Q).  Per point the complex
+// 2-vector g = sum_f conj(w_f) H_f v does not depend on k, so S_k costs 4 FMAs per point.  The second stage (reduce_finish)
+// keeps the fixed order: the sums are bitwise the same run to run and, all-reduced, on every rank.
+template <int M, int VEC, bool NTH>
+__global__ void __launch_bounds__(kThreads) hopf_contract_kernel(size_t N, HopfStreams S, CglCoef c, double* __restrict__ partials) {
+    constexpr int NV = 2 * (M + 2);
+    double s[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s[k] = 0.0;
+    // one grid point: u = (u1, u2), v = (vr1 + i vi1, vr2 + i vi2), w likewise, X_k = (x1[k], x2[k])
+    auto elem = [&](double u1, double u2, double vr1, double vr2, double vi1, double vi2, double wr1, double wr2, double wi1,
+                    double wi2, const double* x1, const double* x2) {
+        if (M > 0) {
+            double h[6];
+            cgl_hess(c, u1, u2, h);
+            // A_f = H_f vr, B_f = H_f vi
+            const double A10 = h[0] * vr1 + h[1] * vr2, A11 = h[1] * vr1 + h[2] * vr2;
+            const double B10 = h[0] * vi1 + h[1] * vi2, B11 = h[1] * vi1 + h[2] * vi2;
+            const double A20 = h[3] * vr1 + h[4] * vr2, A21 = h[4] * vr1 + h[5] * vr2;
+            const double B20 = h[3] * vi1 + h[4] * vi2, B21 = h[4] * vi1 + h[5] * vi2;
+            // g = sum_f (wr_f - i wi_f) (A_f + i B_f)
+            const double gr0 = (wr1 * A10 + wi1 * B10) + (wr2 * A20 + wi2 * B20);
+            const double gr1 = (wr1 * A11 + wi1 * B11) + (wr2 * A21 + wi2 * B21);
+            const double gi0 = (wr1 * B10 - wi1 * A10) + (wr2 * B20 - wi2 * A20);
+            const double gi1 = (wr1 * B11 - wi1 * A11) + (wr2 * B21 - wi2 * A21);
+#pragma unroll
+            for (int k = 0; k < M; ++k) {
+                s[2 * k] = fma(gr0, x1[k], fma(gr1, x2[k], s[2 * k]));
+                s[2 * k + 1] = fma(gi0, x1[k], fma(gi1, x2[k], s[2 * k + 1]));
+            }
+        }
+        double d[4];
+        cgl_djdp(c.ipar, u1, u2, d);
+        const double Ar1 = d[0] * vr1 + d[1] * vr2, Ar2 = d[2] * vr1 + d[3] * vr2;
+        const double Br1 = d[0] * vi1 + d[1] * vi2, Br2 = d[2] * vi1 + d[3] * vi2;
+        s[2 * M] += (wr1 * Ar1 + wi1 * Br1) + (wr2 * Ar2 + wi2 * Br2);
+        s[2 * M + 1] += (wr1 * Br1 - wi1 * Ar1) + (wr2 * Br2 - wi2 * Ar2);
+        s[2 * M + 2] += (wr1 * vr1 + wi1 * vi1) + (wr2 * vr2 + wi2 * vi2);
+        s[2 * M + 3] += (wr1 * vi1 - wi1 * vr1) + (wr2 * vi2 - wi2 * vr2);
+    };
+    if (VEC == 2) {
+        // N even and every stream 16-B aligned in both fields (the launcher checks): N / 2 items, no ragged element
+        stream_loop<1>(N >> 1, [&](auto, size_t i, size_t) {
+            const double2 u1 = ld2<NTH>(S.u, i), u2 = ld2<NTH>(S.u + N, i);
+            const double2 vr1 = ld2<NTH>(S.vr, i), vr2 = ld2<NTH>(S.vr + N, i);
+            const double2 vi1 = ld2<NTH>(S.vi, i), vi2 = ld2<NTH>(S.vi + N, i);
+            const double2 wr1 = ld2<NTH>(S.wr, i), wr2 = ld2<NTH>(S.wr + N, i);
+            const double2 wi1 = ld2<NTH>(S.wi, i), wi2 = ld2<NTH>(S.wi + N, i);
+            double2 x1[M > 0 ? M : 1], x2[M > 0 ? M : 1];
+#pragma unroll
+            for (int k = 0; k < M; ++k) { x1[k] = ld2<NTH>(S.x[k], i); x2[k] = ld2<NTH>(S.x[k] + N, i); }
+            double xa1[M > 0 ? M : 1], xa2[M > 0 ? M : 1], xb1[M > 0 ? M : 1], xb2[M > 0 ? M : 1];
+#pragma unroll
+            for (int k = 0; k < M; ++k) { xa1[k] = x1[k].x; xa2[k] = x2[k].x; xb1[k] = x1[k].y; xb2[k] = x2[k].y; }
+            elem(u1.x, u2.x, vr1.x, vr2.x, vi1.x, vi2.x, wr1.x, wr2.x, wi1.x, wi2.x, xa1, xa2);
+            elem(u1.y, u2.y, vr1.y, vr2.y, vi1.y, vi2.y, wr1.y, wr2.y, wi1.y, wi2.y, xb1, xb2);
+        });
+    } else {
+        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < N; i += (size_t)gridDim.x * kThreads) {
+            double xa1[M > 0 ? M : 1], xa2[M > 0 ? M : 1];
+#pragma unroll
+            for (int k = 0; k < M; ++k) { xa1[k] = S.x[k][i]; xa2[k] = S.x[k][i + N]; }
+            elem(S.u[i], S.u[i + N], S.vr[i], S.vr[i + N], S.vi[i], S.vi[i + N], S.wr[i], S.wr[i + N], S.wi[i], S.wi[i + N],
+                 xa1, xa2);
+        }
+    }
+    __shared__ double sm[NV][4];
+    const int lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const double t = wave_sum(s[k]);
+        if (lane == 0) sm[k][wv_] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        const int k = threadIdx.x;
+        partials[(size_t)blockIdx.x * NV + k] = (sm[k][0] + sm[k][1]) + (sm[k][2] + sm[k][3]);
+    }
+}
+
+static int v_hopf_pw(bk_ctx* ctx, size_t n, const double* u, const CglCoef& c, const double* x1, const double* x2, double* out) {
+    const size_t N = n / 2;
+    if (N == 0) return 0;
+    ProfScope ps(ctx, "blas1", 8.0 * n * (x2 ? 4 : 3));
+    hipLaunchKernelGGL(hopf_pw_kernel, dim3(grid_for(N, 1, 4096)), dim3(kThreads), 0, ctx->stream, N, u, c, x1, x2, out);
+    BK_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// out[2 (m + 2)]: (S_0, ..., S_{m-1}, P, Q) as (re, im) pairs; n = 2 N, the local length of both fields
+static int v_hopf_contract(bk_ctx* ctx, size_t n, const double* u, const double* vr, const double* vi, const double* wr,
+                           const double* wi, int m, const double* const* X, const CglCoef& c, double* out) {
+    if (m < 0 || m > 3) return set_error(ctx, "v_hopf_contract: 0 <= m <= 3 (got %d)", m);
+    const size_t N = n / 2;
+    HopfStreams S{u, vr, vi, wr, wi, {nullptr, nullptr, nullptr}};
+    auto al = [N](const double* p) { return aligned16(p) && aligned16(p + N); };
+    bool vec = (N % 2 == 0) && al(u) && al(vr) && al(vi) && al(wr) && al(wi);
+    for (int k = 0; k < m; ++k) { S.x[k] = X[k]; vec = vec && al(X[k]); }
+    const bool nth = vec && nt_hint(ctx, n);
+    const int grid = grid_for(N, vec ? 2 : 1, kRedBlocks);
+    {
+        ProfScope ps(ctx, "hopf_contract", 8.0 * n * (5 + m));
+#define BK_HC(M)                                                                                                                        \
+    do {                                                                                                                                \
+        if (nth) hipLaunchKernelGGL((hopf_contract_kernel<M, 2, true>), dim3(grid), dim3(kThreads), 0, ctx->stream, N, S, c, ctx->d_partials); \
+        else if (vec) hipLaunchKernelGGL((hopf_contract_kernel<M, 2, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, N, S, c, ctx->d_partials); \
+        else hipLaunchKernelGGL((hopf_contract_kernel<M, 1, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, N, S, c, ctx->d_partials); \
+    } while (0)
+        switch (m) {
+            case 0: BK_HC(0); break;
+            case 1: BK_HC(1); break;
+            case 2: BK_HC(2); break;
+            default: BK_HC(3); break;
+        }
+#undef BK_HC
+        BK_HIP(ctx, hipGetLastError());
+    }
+    const int nv = 2 * (m + 2);
+    BK_TRY(reduce_finish(ctx, grid, nv, 0));
+    for (int k = 0; k < nv; ++k) out[k] = ctx->h_red[k];
+    return 0;
+}
+
+// ------------------------------------------------------------------ the formulation
+int hopf_coef(bk_problem* prob, const double* params, int nparams, int ipar, CglCoef* c) {
+    bk_ctx* ctx = prob->ctx;
+    if (prob->desc.pde != BK_PDE_CGL2D)
+        return set_error(ctx, "hopf: the minimally augmented Hopf formulation is available for BK_PDE_CGL2D only "
+                              "(analytic Hessian of the cGL nonlinearity), not for problem kind %d", prob->desc.pde);
+    if (nparams != 6) return set_error(ctx, "hopf: BK_PDE_CGL2D takes params = {r, mu, nu, c3, c5, gamma} (got %d)", nparams);
+    if (ipar < 0 || ipar > 5) return set_error(ctx, "hopf: bad parameter index %d", ipar);
+    c->mu = params[1]; c->c3 = params[3]; c->c5 = params[4]; c->ipar = ipar;
+    return 0;
+}
+
+// normN of BorderedArray(F, [Re sigma, Im sigma]); the max norm propagates a NaN from any component (as v_nrminf does)
+int norm_hopf(bk_ctx* ctx, size_t n, const double* f, const double sigma[2], bool inf, double* out) {
+    double r;
+    if (inf) {
+        BK_TRY(v_nrminf(ctx, n, f, &r));
+        double s = std::fabs(sigma[0]);
+        const double t = std::fabs(sigma[1]);
+        if (t != t || t > s) s = t;
+        *out = (r != r || r > s) ? r : s;
+    } else {
+        BK_TRY(v_nrm2(ctx, n, f, &r));
+        *out = std::sqrt(r * r + sigma[0] * sigma[0] + sigma[1] * sigma[1]);
+    }
+    return 0;
+}
+
+// _compute_bordered_vectors (:49-64): v, sigma from bls(J, a, b, 0, 0, 1; shift = -i omega), w from the adjoint handle,
+// bls(J', b, a, 0, 0, 1; shift = +i omega).  One BorderingBLS BEC pass each (bk_bls_bordering_cshift).
+int hopf_terms(bk_ctx* ctx, bk_op* J, bk_op* Jt, size_t n, double omega, const double* ar, const double* ai, const double* br,
+               const double* bi, const bk_gmres_opts& lo, bk_precond* pl, double* zero, double* vr, double* vi, double* wr,
+               double* wi, double sigma[2], int* cv, int it[2]) {
+    BK_TRY(v_zero(ctx, n, zero));
+    int c1 = 0, c2 = 0, i1[2] = {0, 0}, i2[2] = {0, 0};
+    double s2[2];
+    BK_TRY(bk_bls_bordering_cshift(ctx, J, ar, ai, br, bi, 0.0, 0.0, zero, nullptr, 1.0, 0.0, 1.0, 1.0, 0.0, -omega, 1.0, &lo, pl,
+                                   vr, vi, sigma, &c1, i1));
+    BK_TRY(bk_bls_bordering_cshift(ctx, Jt, br, bi, ar, ai, 0.0, 0.0, zero, nullptr, 1.0, 0.0, 1.0, 1.0, 0.0, omega, 1.0, &lo, pl,
+                                   wr, wi, s2, &c2, i2));
+    *cv = c1 & c2;
+    it[0] = i1[0] + i1[1];
+    it[1] = i2[0] + i2[1];
+    return 0;
+}
+
+// _hopf_MA_linear_solver, usehessian branch (:142-198), for nrhs right-hand sides sharing the J \ dpF solve:
+//   x1_k = J \ rhsu_k, x2 = J \ dpF;  S(y) = w^H d2F[v, y], sigma_p = -w^H dJ/dp v, sigma_omega = i w^H v;
+//   (sigma_p + S(x2)) dp_k + sigma_omega domega_k = (rhsp_k + i rhsw_k) + S(x1_k)   -- a 2 x 2 real system --
+//   dX_k = x1_k - dp_k x2.
+// Every sum comes from ONE fused pass (v_hopf_contract).  rhspw / dpw: host (p, omega) pairs per right-hand side.  The Hessian
+// and dJ/dp coefficients are taken from `params`, the parameters of the point J belongs to (mu, c3 and c5 enter d2F).
+int hopf_linsolve(bk_ctx* ctx, bk_problem* prob, bk_op* J, const double* x, const double* params, int nparams, int ipar,
+                  const double* vr, const double* vi, const double* wr, const double* wi, int nrhs, const double* const* rhsu,
+                  const double* rhspw, const bk_gmres_opts& lo, bk_precond* pl, double* const* dX, double* dpw, int* cv,
+                  int* itlinear) {
+    const size_t n = prob->nloc;
+    CglCoef c;
+    BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));
+    WsGuard ws(ctx);
+    double *dpF = nullptr, *x2 = nullptr;
+    BK_TRY(ws.get(n, &dpF));
+    BK_TRY(ws.get(n, &x2));
+    BK_TRY(pde_dparam(ctx, prob->desc.pde, c.ipar, n / 2, 1.0, x, dpF));           // analytic dpF
+    GmresResult r0, r1, r2;
+    BK_TRY(linsolve2(ctx, J, rhsu[0], dX[0], dpF, x2, 0.0, 1.0, lo, pl, &r0, &r2));
+    int cvv = r0.converged & r2.converged, its = r0.niter + r2.niter;
+    if (nrhs == 2) {
+        BK_TRY(linsolve(ctx, J, rhsu[1], dX[1], 0.0, 1.0, lo, pl, &r1));
+        cvv &= r1.converged;
+        its += r1.niter;
+    }
+    const double* X[3] = {dX[0], nrhs == 2 ? dX[1] : x2, x2};
+    double s[10];
+    BK_TRY(v_hopf_contract(ctx, n, x, vr, vi, wr, wi, nrhs + 1, X, c, s));
+    const int m = nrhs + 1;
+    const double s2r = s[2 * nrhs], s2i = s[2 * nrhs + 1];
+    const double spr = -s[2 * m], spi = -s[2 * m + 1];                  // sigma_p = -P
+    const double swr = -s[2 * m + 3], swi = s[2 * m + 2];               // sigma_omega = i Q
+    const double a11 = spr + s2r, a12 = swr, a21 = spi + s2i, a22 = swi;
+    const double det = a11 * a22 - a12 * a21;
+    if (!(det != 0.0) || !std::isfinite(det)) return set_error(ctx, "hopf: singular 2 x 2 system of the Hopf linear solver");
+    for (int k = 0; k < nrhs; ++k) {
+        const double b1 = rhspw[2 * k] + s[2 * k], b2 = rhspw[2 * k + 1] + s[2 * k + 1];
+        const double dp = (b1 * a22 - a12 * b2) / det, dw = (a11 * b2 - a21 * b1) / det;
+        dpw[2 * k] = dp;
+        dpw[2 * k + 1] = dw;
+        BK_TRY(v_axpby(ctx, n, -dp, x2, 1.0, dX[k]));
+    }
+    *cv = cvv;
+    *itlinear = its;
+    return 0;
+}
+
+int hopf_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear, double p) {
+    if (no->max_residual > 0.0 && !(residual < no->max_residual)) return 0;
+    if (no->callback) return no->callback(no->callback_user, x, fx, residual, step, itlinear, p, nullptr, NAN, 1) != 0;
+    return 1;
+}
+
+int hopf_check(bk_ctx* ctx, bk_problem* prob) {
+    if (prob->ctx != ctx) return set_error(ctx, "hopf: the problem belongs to another context");
+    return 0;
+}
+
+// the Jacobian and its adjoint at (x, params); both destroyed by the guard
+struct JPair {
+    bk_op* J = nullptr;
+    bk_op* Jt = nullptr;
+    ~JPair() { if (J) bk_op_destroy(J); if (Jt) bk_op_destroy(Jt); }
+    int make(bk_problem* prob, const double* x, const double* par, int np) {
+        BK_TRY(bk_jacobian(prob, x, par, np, &J));
+        return bk_jacobian_adjoint(prob, x, par, np, &Jt);
+    }
+};
+
+}  // namespace
+}  // namespace bk
+
+using namespace bk;
+
+extern "C" {
+
+int bk_hopf_d2f(bk_problem* prob, const double* u, const double* params, int nparams, const double* dx1, const double* dx2,
+                double* out) {
+    if (!prob || !u || !params || !dx1 || !dx2 || !out) return -1;
+    CglCoef c;
+    BK_TRY(hopf_coef(prob, params, nparams, 0, &c));
+    return v_hopf_pw(prob->ctx, prob->nloc, u, c, dx1, dx2, out);
+}
+
+int bk_hopf_djdp(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* dx, double* out) {
+    if (!prob || !u || !params || !dx || !out) return -1;
+    CglCoef c;
+    BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));
+    return v_hopf_pw(prob->ctx, prob->nloc, u, c, dx, nullptr, out);
+}
+
+int bk_hopf_contract(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* v_re,
+                     const double* v_im, const double* w_re, const double* w_im, int m, const double* const* X, double* out) {
+    if (!prob || !u || !params || !v_re || !v_im || !w_re || !w_im || !out || (m > 0 && !X)) return -1;
+    CglCoef c;
+    BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));
+    if (m < 0 || m > 3) return set_error(prob->ctx, "bk_hopf_contract: 0 <= m <= 3 (got %d)", m);
+    for (int k = 0; k < m; ++k)
+        if (!X[k]) return -1;
+    return v_hopf_contract(prob->ctx, prob->nloc, u, v_re, v_im, w_re, w_im, m, X, c, out);
+}
+
+int bk_hopf_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar, double omega,
+                  const double* a_re, const double* a_im, const double* b_re, const double* b_im, const bk_gmres_opts* lsopts,
+                  bk_precond* pl, double* v_re, double* v_im, double* w_re, double* w_im, double sigma[2], double sigma_p[2],
+                  double sigma_omega[2], int* converged, int itlinear[2]) {
+    if (!ctx || !prob || !x || !params || !a_re || !b_re || !lsopts || !v_re || !v_im || !w_re || !w_im || !sigma) return -1;
+    BK_TRY(hopf_check(ctx, prob));
+    CglCoef c;
+    BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));
+    const double* outs[4] = {v_re, v_im, w_re, w_im};
+    const double* ins[5] = {a_re, a_im, b_re, b_im, x};
+    for (int k = 0; k < 4; ++k) {
+        for (const double* i : ins)
+            if (outs[k] == i) return set_error(ctx, "bk_hopf_terms: v and w must not alias a, b or x");
+        for (int j = 0; j < k; ++j)
+            if (outs[k] == outs[j]) return set_error(ctx, "bk_hopf_terms: v_re, v_im, w_re and w_im must be distinct");
+    }
+    const size_t n = prob->nloc;
+    WsGuard ws(ctx);
+    double* zero = nullptr;
+    BK_TRY(ws.get(n, &zero));
+    int cv = 0, it[2] = {0, 0};
+    {
+        JPair jp;
+        BK_TRY(jp.make(prob, x, params, nparams));
+        BK_TRY(hopf_terms(ctx, jp.J, jp.Jt, n, omega, a_re, a_im, b_re, b_im, *lsopts, pl, zero, v_re, v_im, w_re, w_im, sigma,
+                          &cv, it));
+    }
+    if (sigma_p || sigma_omega) {
+        double s[4];
+        BK_TRY(v_hopf_contract(ctx, n, x, v_re, v_im, w_re, w_im, 0, nullptr, c, s));
+        if (sigma_p) { sigma_p[0] = -s[0]; sigma_p[1] = -s[1]; }
+        if (sigma_omega) { sigma_omega[0] = -s[3]; sigma_omega[1] = s[2]; }
+    }
+    if (converged) *converged = cv;
+    if (itlinear) { itlinear[0] = it[0]; itlinear[1] = it[1]; }
+    return 0;
+}
+
+int bk_hopf_linsolve(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar,
+                     const double* v_re, const double* v_im, const double* w_re, const double* w_im, int nrhs,
+                     const double* const* rhsu, const double* rhspw, const bk_gmres_opts* lsopts, bk_precond* pl,
+                     double* const* dX, double* dpw, int* converged, int* itlinear) {
+    if (!ctx || !prob || !x || !params || !v_re || !v_im || !w_re || !w_im || !rhsu || !rhspw || !lsopts || !dX || !dpw) return -1;
+    BK_TRY(hopf_check(ctx, prob));
+    CglCoef c;
+    BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));                // validates the problem kind and parameters up front
+    if (nrhs < 1 || nrhs > 2) return set_error(ctx, "bk_hopf_linsolve: 1 or 2 right-hand sides (got %d)", nrhs);
+    for (int k = 0; k < nrhs; ++k) {
+        if (!rhsu[k] || !dX[k]) return -1;
+        for (int j = 0; j < nrhs; ++j)
+            if (dX[k] == rhsu[j]) return set_error(ctx, "bk_hopf_linsolve: dX must not alias a right-hand side");
+    }
+    if (nrhs == 2 && dX[0] == dX[1]) return set_error(ctx, "bk_hopf_linsolve: dX[0] and dX[1] must be distinct");
+    bk_op* J = nullptr;
+    BK_TRY(bk_jacobian(prob, x, params, nparams, &J));
+    int cv = 0, it = 0;
+    int s = hopf_linsolve(ctx, prob, J, x, params, nparams, ipar, v_re, v_im, w_re, w_im, nrhs, rhsu, rhspw, *lsopts, pl, dX,
+                          dpw, &cv, &it);
+    bk_op_destroy(J);
+    BK_TRY(s);
+    if (converged) *converged = cv;
+    if (itlinear) *itlinear = it;
+    return 0;
+}
+
+int bk_newton_hopf(bk_ctx* ctx, bk_problem* prob, double* x, double* p, double* omega, const double* params, int nparams,
+                   int ipar, const double* a_re, const double* a_im, const double* b_re, const double* b_im,
+                   const bk_newton_opts* no, const bk_gmres_opts* lsopts, bk_precond* pl, double* v_re, double* v_im,
+                   double* w_re, double* w_im, double sigma[2], bk_newton_result* res) {
+    if (!ctx || !prob || !x || !p || !omega || !params || !a_re || !b_re || !no || !lsopts || !v_re || !v_im || !w_re || !w_im ||
+        !sigma || !res)
+        return -1;
+    BK_TRY(hopf_check(ctx, prob));
+    if (no->max_iterations > BK_MAX_NEWTON_ITER) return set_error(ctx, "max_iterations > %d", BK_MAX_NEWTON_ITER);
+    CglCoef c;
+    BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));                // validates the problem kind and parameters up front
+    const double* outs[5] = {v_re, v_im, w_re, w_im, x};
+    const double* ins[4] = {a_re, a_im, b_re, b_im};
+    for (int i = 0; i < 5; ++i) {
+        for (const double* q : ins)
+            if (outs[i] == q) return set_error(ctx, "bk_newton_hopf: x, v and w must be distinct from a and b and from each other");
+        for (int j = 0; j < i; ++j)
+            if (outs[i] == outs[j]) return set_error(ctx, "bk_newton_hopf: x, v and w must be distinct from a and b and from each other");
+    }
+    const size_t n = prob->nloc;
+    const bool inf = no->norm_inf != 0;
+    WsGuard ws(ctx);
+    double *fx = nullptr, *dX = nullptr, *zero = nullptr;
+    BK_TRY(ws.get(n, &fx));
+    BK_TRY(ws.get(n, &dX));
+    BK_TRY(ws.get(n, &zero));
+    double par[BK_MAX_PARAMS];
+    for (int i = 0; i < nparams; ++i) par[i] = params[i];
+    double pc = *p, wc = *omega;
+    int itlin = 0;
+    // one evaluation of the Hopf residual (:22-45) at (x, pc, wc), with the bordered vectors v, w of this point, which the
+    // Newton step at the same point reuses (the reference solves them again in _get_bordered_terms)
+    auto point = [&](double* r) -> int {
+        par[ipar] = pc;
+        int cv = 0, it[2] = {0, 0};
+        {
+            JPair jp;
+            BK_TRY(jp.make(prob, x, par, nparams));
+            BK_TRY(hopf_terms(ctx, jp.J, jp.Jt, n, wc, a_re, a_im, b_re, b_im, *lsopts, pl, zero, v_re, v_im, w_re, w_im, sigma,
+                              &cv, it));
+        }
+        itlin += it[0] + it[1];
+        if (!cv) ctx->diag.hopf_unconverged += 1.0;
+        BK_TRY(bk_residual(prob, x, par, nparams, fx));
+        return norm_hopf(ctx, n, fx, sigma, inf, r);
+    };
+    double r;
+    BK_TRY(point(&r));
+    int step = 0;
+    res->residuals[0] = r;
+    int compute = hopf_cb(no, x, fx, r, 0, 0, pc);
+    while (step < no->max_iterations && r > no->tol && compute) {
+        // Newton step: J_hopf [dX; dp; domega] = [F; Re sigma; Im sigma] (HopfLinearSolverMinAug), x -= dX, (p, omega) -= (dp, domega)
+        par[ipar] = pc;
+        bk_op* J = nullptr;
+        BK_TRY(bk_jacobian(prob, x, par, nparams, &J));
+        const double* rhsu[1] = {fx};
+        double* dXs[1] = {dX};
+        double dpw[2] = {0.0, 0.0};
+        int cv = 0, it = 0;
+        // the coefficients of d2F and dJ/dp follow the current parameter value (par), not the caller's params
+        int s = hopf_linsolve(ctx, prob, J, x, par, nparams, ipar, v_re, v_im, w_re, w_im, 1, rhsu, sigma, *lsopts, pl, dXs, dpw,
+                              &cv, &it);
+        bk_op_destroy(J);
+        BK_TRY(s);
+        itlin += it;
+        if (!cv) ctx->diag.hopf_unconverged += 1.0;
+        BK_TRY(v_axpby(ctx, n, -1.0, dX, 1.0, x));
+        pc -= dpw[0];
+        wc -= dpw[1];
+        const int before = itlin;
+        BK_TRY(point(&r));
+        step += 1;
+        res->residuals[step] = r;
+        compute = hopf_cb(no, x, fx, r, step, it + (itlin - before), pc);
+    }
+    *p = pc;
+    *omega = wc;
+    res->converged = (res->residuals[step] < no->tol) & hopf_cb(no, x, fx, r, step, 0, pc);
+    res->itnewton = step;
+    res->itlinear = itlin;
+    return 0;
+}
+
+}  // extern "C"

@@ -512,6 +512,50 @@ int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
                    const bk_gmres_opts* lsopts, bk_precond* pl, double* v, double* w, double* sigma,
                    bk_newton_result* res);
 
+/* ------------------------------------------------------------------ Hopf points (codim 2) ---------------
+ * The minimally augmented Hopf formulation of src/codim2/MinAugHopf.jl, matrix-free: unknowns (x, p = params[ipar], omega),
+ * G = (F(x, p), Re sigma, Im sigma) with sigma from [J - i omega, a; b^H, 0][v; sigma] = [0; 1] and w from the adjoint system
+ * [J' + i omega, b; a^H, 0][w; sigma2] = [0; 1].  With w^H a = 1: sigma_x . dx = -w^H d2F[v, dx], sigma_p = -w^H dJ/dp v,
+ * sigma_omega = i w^H v.  Defined for BK_PDE_CGL2D only (its nonlinearity is pointwise with an analytic Hessian); any other
+ * problem returns an error.  Complex device vectors are (re, im) pairs of real vectors of the problem's local length; an *_im
+ * input may be NULL (= 0) where noted.  J is regular at a Hopf point, so the real solves J \ . need no bordering.          */
+/* out = d2F(u, params)[dx1, dx2] for real dx1, dx2: per grid point the symmetric 2 x 2 Hessians of the cGL nonlinearity
+ * (examples/cGL2d.jl:24-40); complex arguments by linearity.                                                            */
+int bk_hopf_d2f(bk_problem* prob, const double* u, const double* params, int nparams, const double* dx1, const double* dx2,
+                double* out);
+/* out = dJ/dp(u) dx for params[ipar] = (r, mu, nu, c3, c5, gamma): the u-derivative of the pointwise dF/dp (zero for gamma). */
+int bk_hopf_djdp(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* dx, double* out);
+/* One streaming pass over u, v, w and m <= 3 real device vectors X[k]: host out[2 (m + 2)] = (re, im) pairs of
+ * S_k = w^H d2F(u)[v, X_k] (k < m), P = w^H dJ/dp(u) v for params[ipar], Q = w^H v.  Deterministic, all-reduced.           */
+int bk_hopf_contract(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* v_re,
+                     const double* v_im, const double* w_re, const double* w_im, int m, const double* const* X, double* out);
+/* _compute_bordered_vectors + _get_bordered_terms (MinAugHopf.jl) at (x, params, omega): v, sigma from
+ * bk_bls_bordering_cshift(J, a, b, 0, 0, 1; shift = -i omega), w from the same on the adjoint handle with a and b exchanged and
+ * shift = +i omega (a_im, b_im may be NULL).  sigma[2], and (each may be NULL) sigma_p[2] = -w^H dJ/dp v and
+ * sigma_omega[2] = i w^H v.  itlinear[0] / [1]: GMRES counts of the v / w solves.                                        */
+int bk_hopf_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar, double omega,
+                  const double* a_re, const double* a_im, const double* b_re, const double* b_im, const bk_gmres_opts* lsopts,
+                  bk_precond* pl, double* v_re, double* v_im, double* w_re, double* w_im, double sigma[2], double sigma_p[2],
+                  double sigma_omega[2], int* converged, int itlinear[2]);
+/* _hopf_MA_linear_solver, usehessian branch, for nrhs = 1 or 2 right-hand sides (rhsu[k] device, host rhspw[2k], rhspw[2k+1]
+ * = the p and omega rows) with the bordered vectors v, w of (x, params): x1_k = J \ rhsu_k, ONE x2 = J \ dpF shared by all
+ * right-hand sides (dpF analytic), (dp_k, domega_k) from the complex equation
+ * (sigma_p - sigma_x.x2) dp + sigma_omega domega = (rhsp + i rhsomega) - sigma_x.x1 as a 2 x 2 real system, dX_k = x1_k - dp_k x2.
+ * Host dpw[2k], dpw[2k+1] = (dp_k, domega_k).  nrhs + 1 real GMRES solves (the reference: 2 nrhs).                        */
+int bk_hopf_linsolve(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar,
+                     const double* v_re, const double* v_im, const double* w_re, const double* w_im, int nrhs,
+                     const double* const* rhsu, const double* rhspw, const bk_gmres_opts* lsopts, bk_precond* pl,
+                     double* const* dX, double* dpw, int* converged, int* itlinear);
+/* newton_hopf under the semantics of _newton (src/Newton.jl:66-114), as bk_newton_fold: (x, *p, *omega) = guess on entry, Hopf
+ * point on exit; tol applies to BorderedArray(F, [Re sigma, Im sigma]) in the chosen norm; callback as bk_newton (p = the
+ * Hopf parameter).  Each point's v and w are solved once and serve its residual and its Newton step.  On exit v, w and sigma
+ * are those of the returned point.  Each unconverged bordered-vector or step solve adds 1 to the context counter
+ * "hopf_unconverged_solves".                                                                                            */
+int bk_newton_hopf(bk_ctx* ctx, bk_problem* prob, double* x, double* p, double* omega, const double* params, int nparams,
+                   int ipar, const double* a_re, const double* a_im, const double* b_re, const double* b_im,
+                   const bk_newton_opts* nopts, const bk_gmres_opts* lsopts, bk_precond* pl, double* v_re, double* v_im,
+                   double* w_re, double* w_im, double sigma[2], bk_newton_result* res);
+
 #ifdef __cplusplus
 }
 #endif
