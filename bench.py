@@ -35,8 +35,14 @@ predictor, so the work per step is identical and nothing is cached between steps
 before the timed region; synthetic data (the reference's own initial guess, Newton-converged on the device).
 
 Prints ONE JSON line (rank 0).  `roofline` is for the kernel with the largest share of the timed region,
-measured with HIP events on the library's stream (bk_prof_*); `cpu_baseline` times the NumPy/SciPy oracle
-(reference formulation: assembled sparse L1, MGS2 GMRES) on a bounded sample on this host.
+measured with HIP events on the library's stream (bk_prof_*) during the timed steps themselves.
+
+A plain run does what the headline figure needs and no more: setup, warm-up, the timed steps, `--dump-outputs`, the line.
+`--full` adds everything that takes runs of its own, and the records that are null without it: the run-to-convergence
+correctors on the big grid and on the cell (`config.full_corrector` / `cell_corrector`, `comm.parity_vs_1rank`), the residuals
+of the tiled states, `fixed_input`, `steady_state`, the communicator probes of a multi-GPU run, and `cpu_baseline`, which times
+the NumPy/SciPy oracle (reference formulation: assembled sparse L1, MGS2 GMRES) and its C++/OpenMP restatement on bounded
+samples on this host.  The timed steps and their inputs are the same with and without it.
 
 `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (float64; the state as a fixed, seeded
 sample of at most DUMP_STATE_MAX values), so that two builds run with the same arguments can be compared output for output.
@@ -98,6 +104,12 @@ def parse():
     ap.add_argument("--linsolver", default="gmres", choices=["gmres", "minres"],
                     help="gmres: GMRESKrylovKit(30), the reference example's solver (the headline workload); minres: "
                          "KrylovLS(KrylovAlg = :minres), valid because the SH Jacobian is symmetric (experiment)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything next to the headline figure: the run-to-convergence correctors of the setup and their parity "
+                         "check, the residuals of the tiled states, the fixed_input and steady_state records, the CPU baselines and the "
+                         "communicator probes (--no-full / --no-fixed / --no-steady / --cpu-sample 0 drop single ones of them).  Without "
+                         "it a run sets up, warms up, times the steps and prints the line; those records are null.  A --workload branch "
+                         "line reports none of them: --full adds nothing to it but the time of the setup's correctors")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64; a state "
                          f"longer than {DUMP_STATE_MAX} values as a fixed seeded sample of that many) so that two builds can be "
@@ -420,25 +432,30 @@ def main():
     p0, p1 = 0.1, 0.1 + ds / 150.0
     u0 = hip.HipVec(ctx, tile_cell(c0["u"].t, tiles, prob.slab, ctx.torch_device), prob.nglobal)
     u1 = hip.HipVec(ctx, tile_cell(c1["u"].t, tiles, prob.slab, ctx.torch_device), prob.nglobal)
-    res0 = prob.residual(u0, p0).norminf()           # the tiled field is an exact discrete solution
-    res1 = prob.residual(u1, p1).norminf()
+    res0 = prob.residual(u0, p0).norminf() if args.full else None       # the tiled field is an exact discrete solution
+    res1 = prob.residual(u1, p1).norminf() if args.full else None
     z0, z1 = B(u0, p0), B(u1, p1)
     tau = z1.copy().add_(z0, -1.0)
     nrm = math.sqrt(tau.u.inner(tau.u) / prob.nglobal * theta + tau.p * tau.p * (1 - theta))
     tau.scale_(math.copysign(1.0, ds) / nrm)                                        # Secant tangent, Tangents.jl:28-42
     z_pred = z0.copy().add_(tau, ds)
-    none_ = {"converged": None, "itnewton": None, "itlineartot": None, "residuals": [], "u": B(u0, float("nan"))}
-    full = none_ if args.no_full else hip.newton_palc_native(prob, z0, tau, z_pred, ds, theta, bls, tol=1e-9, max_iterations=15,
-                                                            p_min=-0.1, p_max=0.15, norm_inf=True)
-    # the same corrector on the single cell: must give the same trajectory
-    cb_ = hip.BorderedArray
-    cz0, cz1 = cb_(c0["u"], p0), cb_(c1["u"], p1)
-    ctau = cz1.copy().add_(cz0, -1.0)
-    cn = math.sqrt(ctau.u.inner(ctau.u) / cprob.nglobal * theta + ctau.p * ctau.p * (1 - theta))
-    ctau.scale_(math.copysign(1.0, ds) / cn)
-    cfull = none_ if args.no_full else hip.newton_palc_native(cprob, cz0, ctau, cz0.copy().add_(ctau, ds), ds, theta,
-                                                             hip.BorderingBLS(cls_, check_precision=False), tol=1e-9, max_iterations=15,
-                                                             p_min=-0.1, p_max=0.15, norm_inf=True)
+    # the run-to-convergence correctors (--full): on the big grid and, the same corrector, on the single cell -- it must give
+    # the same trajectory.  A record of a corrector that did not run is null throughout.
+    import types
+    none_ = {"converged": None, "itnewton": None, "itlineartot": None, "residuals": [], "u": types.SimpleNamespace(p=None)}
+    run_full = args.full and not args.no_full
+    full = cfull = none_
+    if run_full:
+        full = hip.newton_palc_native(prob, z0, tau, z_pred, ds, theta, bls, tol=1e-9, max_iterations=15,
+                                      p_min=-0.1, p_max=0.15, norm_inf=True)
+        cb_ = hip.BorderedArray
+        cz0, cz1 = cb_(c0["u"], p0), cb_(c1["u"], p1)
+        ctau = cz1.copy().add_(cz0, -1.0)
+        cn = math.sqrt(ctau.u.inner(ctau.u) / cprob.nglobal * theta + ctau.p * ctau.p * (1 - theta))
+        ctau.scale_(math.copysign(1.0, ds) / cn)
+        cfull = hip.newton_palc_native(cprob, cz0, ctau, cz0.copy().add_(ctau, ds), ds, theta,
+                                       hip.BorderingBLS(cls_, check_precision=False), tol=1e-9, max_iterations=15,
+                                       p_min=-0.1, p_max=0.15, norm_inf=True)
     barrier()
     t_setup = time.perf_counter() - t_setup
 
@@ -493,7 +510,7 @@ def main():
     # digits of this build's own cell Newton solves, so two builds can be compared by it
     fixed = None
     fx = os.path.join(ROOT, "tests", "golden", "bench_cell_states.npz")
-    if os.path.exists(fx) and not args.no_fixed and args.shift == 1.0:
+    if args.full and os.path.exists(fx) and not args.no_fixed and args.shift == 1.0:
         import numpy as np
         d = np.load(fx)
         if tuple(int(v) for v in d["cell"]) == CELL:
@@ -548,7 +565,7 @@ def main():
     # ---- steady state: the corrector of a RUNNING branch (state, Bordered tangent and step size after two native
     # continuation steps), run to convergence -- next to the first-corrector headline (Weak 2)
     steady = None
-    if not args.no_steady:
+    if args.full and not args.no_steady:
         cp, alg = branch_setup(None)
         cp.max_steps = 2
         grab = {}
@@ -595,14 +612,15 @@ def main():
     comm_rec = None
     if world > 1:
         kind, crank, cranks = ctx.comm_info()
-        ar_us = ctx.comm_probe("allreduce", 32, 50)                 # the projections of one Arnoldi step
+        ar_us = ctx.comm_probe("allreduce", 32, 50) if args.full else None     # the projections of one Arnoldi step
         halo_cnt = 2 * n * n                                        # 2 planes per side
-        halo_us = ctx.comm_probe("halo", halo_cnt, 20)
+        halo_us = ctx.comm_probe("halo", halo_cnt, 20) if args.full else None
         nb = 2 if 0 < rank < world - 1 else 1
         wall_ms = dt * 1e3
         comm_rec = {"backend": kind, "ranks_in_communicator": cranks, "allreduce_32_doubles_us": ar_us,
                     "halo_exchange_us": halo_us, "halo_bytes_per_neighbour": 8 * halo_cnt,
-                    "halo_gbs_per_direction": 8.0 * halo_cnt / max(halo_us, 1e-9) / 1e3, "halo_neighbours_rank0": nb,
+                    "halo_gbs_per_direction": None if halo_us is None else 8.0 * halo_cnt / max(halo_us, 1e-9) / 1e3,
+                    "halo_neighbours_rank0": nb,
                     "share_of_wall": {k_: kernels[k_]["ms_total"] / max(wall_ms, 1e-9) for k_ in ("halo", "alltoall", "transpose")
                                       if k_ in kernels},
                     "note": "halo / alltoall shares are event-timed spans on rank 0's streams (the halo exchange runs on its own "
@@ -611,7 +629,7 @@ def main():
                     # on the one cell, solved by this rank alone on a single-rank context (no communicator) -- the tiling property makes
                     # them the same trajectory (tests/test_gpu_fullsize.py), so p must agree to the solver tolerance and the
                     # operator-application counts to the rounding-noise wobble of the last Arnoldi steps (+-2 per solve)
-                    "parity_vs_1rank": None if args.no_full else {
+                    "parity_vs_1rank": None if not run_full else {
                         "p_distributed": full["u"].p, "p_cell_on_one_rank": cfull["u"].p, "abs_diff_p": abs(full["u"].p - cfull["u"].p),
                         "itlinear_distributed": full["itlineartot"], "itlinear_cell_on_one_rank": cfull["itlineartot"],
                         "itnewton": [full["itnewton"], cfull["itnewton"]],
@@ -722,7 +740,7 @@ def main():
             "roofline": roofline, "inner_loop": inner, "fixed_input": fixed, "steady_state": steady, "kernels": kernels, "comm": comm_rec,
         }
         cb = None
-        if world == 1 and args.cpu_sample > 0:
+        if args.full and world == 1 and args.cpu_sample > 0:
             try:
                 c = cpu_baseline((args.cpu_sample,) * 3, args.shift)
                 scaled = (1.0 / c["seconds_per_step"]) * (c["n"] / prob.nglobal)

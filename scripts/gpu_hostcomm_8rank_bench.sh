@@ -4,24 +4,26 @@
 # the RCCL calls themselves.  Each line must reproduce the 1-rank corrector (itlinear, p, residual).
 set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+mkdir -p "${OUTDIR:-bench_out}" && export OUTDIR="$(cd "${OUTDIR:-bench_out}" && pwd)"   # absolute: the same folder after any cd, and in the scripts this one calls
 export PYTHONPATH="$PWD"
-OUT=gpurun_out/hostcomm_ranks.jsonl
-: > $OUT
+OUT="$OUTDIR"/hostcomm_ranks.jsonl
+: > "$OUT"
 one() {   # size ranks
     timeout ${3:-600} python -m torch.distributed.run --nnodes=1 --nproc-per-node $2 --master-addr 127.0.0.1 --master-port $((29600 + $2 + $1 / 64)) \
-        bench.py --gpus $2 --size $1 --steps 1 --warmup 1 --cpu-sample 0 --no-steady 2> gpurun_out/hostcomm_$1_$2.err | tail -1 >> $OUT
-    tail -c 400 gpurun_out/hostcomm_$1_$2.err | grep -v "^$" | tail -3
+        bench.py --full --gpus $2 --size $1 --steps 1 --warmup 1 --cpu-sample 0 --no-steady 2> "$OUTDIR"/hostcomm_$1_$2.err | tail -1 >> "$OUT"
+    tail -c 400 "$OUTDIR"/hostcomm_$1_$2.err | grep -v "^$" | tail -3
 }
-timeout 300 python bench.py --size 256 --steps 3 --warmup 1 --cpu-sample 0 2>/dev/null | tail -1 > gpurun_out/bench256_1rank.json
-cat gpurun_out/bench256_1rank.json >> $OUT
+timeout 300 python bench.py --full --size 256 --steps 3 --warmup 1 --cpu-sample 0 2>/dev/null | tail -1 > "$OUTDIR"/bench256_1rank.json
+cat "$OUTDIR"/bench256_1rank.json >> "$OUT"
 export BK_BENCH_HOSTCOMM=1
 one 256 8 400
 one 512 8 900
 # one 512 4 900     (4 ranks: covered at small size by tests/test_distributed.py)
 python - <<'PY'
+import os
+O = os.environ["OUTDIR"]
 import json
-for l in open('gpurun_out/hostcomm_ranks.jsonl'):
+for l in open(O + '/hostcomm_ranks.jsonl'):
     try:
         d = json.loads(l)
         c = d['config']

@@ -1,17 +1,19 @@
 #!/bin/bash
 # round 6: MINRES direction / solution update two iterations at a time (option minres_pair_update) -- parity, then A/B on the branch workload
 set -u
-cd "${GRAFT_REPO_ROOT:-/root/repo}"; export PYTHONPATH="$PWD"; mkdir -p gpurun_out
-timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -k "minres or krylovls or symmetric or eig or shift_invert" 2>&1 | tail -6 > gpurun_out/m_pytest.log
-B="python bench.py --workload branch --cpu-sample 0"
+cd "$(dirname "$0")/.."; export PYTHONPATH="$PWD"; mkdir -p "${OUTDIR:-bench_out}" && export OUTDIR="$(cd "${OUTDIR:-bench_out}" && pwd)"
+timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -k "minres or krylovls or symmetric or eig or shift_invert" 2>&1 | tail -6 > "$OUTDIR"/m_pytest.log
+B="python bench.py --full --workload branch --cpu-sample 0"
 for v in 1 0; do
-  timeout 300 $B --size 256 --steps 4 --opt minres_pair_update=$v > gpurun_out/m_branch_256_pair$v.json 2> gpurun_out/m_branch_256_pair$v.err
-  timeout 600 $B --size 512 --steps 2 --opt minres_pair_update=$v > gpurun_out/m_branch_512_pair$v.json 2> gpurun_out/m_branch_512_pair$v.err
+  timeout 300 $B --size 256 --steps 4 --opt minres_pair_update=$v > "$OUTDIR"/m_branch_256_pair$v.json 2> "$OUTDIR"/m_branch_256_pair$v.err
+  timeout 600 $B --size 512 --steps 2 --opt minres_pair_update=$v > "$OUTDIR"/m_branch_512_pair$v.json 2> "$OUTDIR"/m_branch_512_pair$v.err
 done
-tail -4 gpurun_out/m_pytest.log
+tail -4 "$OUTDIR"/m_pytest.log
 python - <<'PY'
+import os
+O = os.environ["OUTDIR"]
 import json, glob
-for f in sorted(glob.glob("gpurun_out/m_branch_*.json")):
+for f in sorted(glob.glob(O + "/m_branch_*.json")):
     try:
         o = json.loads(open(f).read().strip().splitlines()[-1])
         it = sum(p["eig_inner_iterations"] for p in o["per_step"]); sec = sum(p["seconds"] for p in o["per_step"])

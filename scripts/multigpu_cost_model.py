@@ -15,7 +15,8 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out")
+# (default: where scripts/gpu_cost_model_inputs.sh wrote them -- $OUTDIR, else its default bench_out/ in the repository root)
+src = sys.argv[1] if len(sys.argv) > 1 else os.path.abspath(os.environ.get("OUTDIR") or os.path.join(ROOT, "bench_out"))
 one = json.load(open(sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles", "r3_bench_512_1gpu.json")))
 emu = [json.loads(l) for l in open(os.path.join(src, "slabemu.jsonl"))]
 LAT, LINK = 25e-6, 7 * 45e9

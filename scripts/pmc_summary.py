@@ -1,6 +1,6 @@
 """Summarise the two rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; separate runs, --kernel-trace only) into
 profiles/<tag>_pmc_hbm_traffic.{txt,json}: measured HBM bytes per launch of every kernel of the 512^3 bench.
-Usage: python scripts/pmc_summary.py gpurun_out/pmc_fetch_<tag> gpurun_out/pmc_write_<tag> profiles/<tag>"""
+Usage: python scripts/pmc_summary.py $OUTDIR/pmc_fetch_<tag> $OUTDIR/pmc_write_<tag> profiles/<tag>"""
 import collections
 import glob
 import hashlib
@@ -50,7 +50,7 @@ for d, cname in ((fetch_dir, "FETCH_SIZE"), (write_dir, "WRITE_SIZE")):
         med[k][cname] = (len(v), mid, min(v), max(v))
 
 lines = ["# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, --kernel-trace only) over",
-         "#   python bench.py --steps 1 --warmup 0 --cpu-sample 0      (SH3d 512^3, MI355X, ROCm 7.2)",
+         "#   python bench.py --full --steps 1 --warmup 0 --cpu-sample 0 --no-steady      (SH3d 512^3, MI355X, ROCm 7.2)",
          "# Dispatches longer than 300 us only (the 512^3 launches; the one-cell launches are filtered out).",
          "# Units: the counters are in KiB.  gfx950 correction (MI355X_MICROARCH.md, HBM section): FETCH_SIZE reports 1/2 of",
          "# the bytes of wide coalesced reads -> read_bytes = 2 * FETCH_SIZE * 1024.  WRITE_SIZE * 1024 matches the known",
@@ -70,7 +70,7 @@ lines += ["", "# multidot<KB> / multiaxpy<KB>: the median launch has k+1 (k+2) =
           "#   operator: 2 GiB read (the vector + u, or the spectrum + the shifted vector) + 1 GiB written.  The family row is the launch-weighted",
           "#   MEAN.  sh_stream_kernel<true, VL>: algorithmic 2 GiB read (v, u) + 1 GiB written."]
 out["_meta"] = dict(sources_sha=sources_sha(), command="rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace -- python bench.py "
-                    "--steps 1 --warmup 0 --cpu-sample 0 --no-steady")
+                    "--full --steps 1 --warmup 0 --cpu-sample 0 --no-steady")
 lines.append(f"# kernel sources fingerprint (bifurcationkit.jl_amd/csrc/*.hip, *.h): {out['_meta']['sources_sha']}")
 open(out_prefix + "_pmc_hbm_traffic.txt", "w").write("\n".join(lines) + "\n")
 json.dump(out, open(out_prefix + "_pmc_hbm_traffic.json", "w"), indent=1)

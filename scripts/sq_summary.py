@@ -1,5 +1,5 @@
 """Summarise a rocprofv3 SQ-counter pass over the 512^3 bench into a per-kernel stall breakdown.
-Usage: python scripts/sq_summary.py gpurun_out/sq_<tag> [profiles/<tag>_sq_stall_breakdown.txt]
+Usage: python scripts/sq_summary.py $OUTDIR/sq_<tag> [profiles/<tag>_sq_stall_breakdown.txt]
 Counters (one pass, 8 SQ slots; MI355X_MICROARCH.md "rocprofv3 PMC slots"): SQ_WAVE_CYCLES = ACTIVE_INST_ANY + WAIT_ANY
 (wave parked on s_waitcnt / barrier) + WAIT_INST_ANY (issue stall), in quad-cycles summed over waves."""
 import collections
@@ -25,7 +25,7 @@ for k, c, v, dt in rows:
     agg[clean(k)][c].append(v)
     dur[clean(k)].append(dt / 1e3)
 names = sorted({c for k in agg for c in agg[k]})
-lines = ["# rocprofv3 --pmc " + " ".join(names) + " --kernel-trace -- python bench.py --steps 1 --warmup 0 --cpu-sample 0 --no-steady",
+lines = ["# rocprofv3 --pmc " + " ".join(names) + " --kernel-trace -- python bench.py --full --steps 1 --warmup 0 --cpu-sample 0 --no-steady",
          "# SH3d 512^3, dispatches > 300 us; medians per launch; percentages are of SQ_WAVE_CYCLES (quad-cycles summed over waves):",
          "# active = an instruction of the wave issued; wait_any = parked on s_waitcnt / barrier; wait_inst = issue stall;",
          "# valu / lds / vmem = share of wave cycles in which that unit's instruction was issuing; lds_conf = bank-conflict share of LDS cycles", ""]
