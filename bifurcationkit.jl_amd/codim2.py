@@ -14,6 +14,9 @@ path (the reference assembles the systems for MatrixBLS / MinAugMatrixBased, whi
 Problems: SwiftHohenberg (2-D / 3-D) and SwiftHohenberg1D -- symmetric, J' = J (:79-84).  sigma_p, dpF and sigma_x are analytic
 (the Jacobians depend on the parameters only through their pointwise term), where the reference takes central differences.
 The bordered vectors v, w of a point are solved once and serve both its residual and its Newton step.
+
+What the two formulations have in common is written once: _MinAugProblem (the cached bordered vectors and the problem surface),
+_MinAugLinearSolver, _continuation_minaug (the PALC loop) and _newton_minaug_mirror (the Newton loop of the mirrors).
 """
 from __future__ import annotations
 
@@ -29,9 +32,33 @@ from . import continuation as Cn
 from .hip import BorderedArray, BorderingBLS, HipVec, _GMRES, _ptr, newton_opts
 
 
+def _nanmax(*vals):
+    """max that propagates a NaN from any argument (Python's max drops it depending on the argument order)."""
+    vals = [float(v) for v in vals]
+    return math.nan if any(v != v for v in vals) else max(vals)
+
+
 def _norm_fold(F, sigma, norm_inf):
-    """normN of BorderedArray(F, sigma): norminf = max(|F|_inf, |sigma|), norm = sqrt(|F|^2 + sigma^2)."""
-    return max(F.norminf(), abs(sigma)) if norm_inf else math.sqrt(F.norm() ** 2 + sigma ** 2)
+    """normN of BorderedArray(F, sigma): norminf = max(|F|_inf, |sigma|), norm = sqrt(|F|^2 + sigma^2); a NaN in either
+    component gives NaN in both norms, as norm_fold of fold.hip."""
+    return _nanmax(F.norminf(), abs(sigma)) if norm_inf else math.sqrt(F.norm() ** 2 + sigma ** 2)
+
+
+def _carr(pars):
+    """The parameter list as the double array of the C API."""
+    return (C.c_double * len(pars))(*pars)
+
+
+def _vptrs(vecs):
+    """The device pointers of HipVecs as an array of const double* (one unused slot when there are none)."""
+    return (C.c_void_p * max(len(vecs), 1))(*[v.t.data_ptr() for v in vecs])
+
+
+def _into_similar(prob, fn: str, x: HipVec, pars, *args) -> HipVec:
+    """out = the library's ``fn``(prob, x, pars, len(pars), *args, out) with a new vector ``out`` like x."""
+    ctx, out = prob.ctx, x.similar()
+    ctx.check(getattr(ctx.lib, fn)(prob.h, _ptr(x.t), _carr(pars), len(pars), *args, _ptr(out.t)), fn)
+    return out
 
 
 def _params(prob, **vals):
@@ -42,49 +69,36 @@ def _params(prob, **vals):
 
 def d2F(prob, x: HipVec, pars, dx1: HipVec, dx2: HipVec) -> HipVec:
     """d2F(prob, x, par, dx1, dx2) (src/Problems.jl:107,165) on the device (bk_d2f)."""
-    ctx, out = prob.ctx, x.similar()
-    arr = (C.c_double * len(pars))(*pars)
-    ctx.check(ctx.lib.bk_d2f(prob.h, _ptr(x.t), arr, len(pars), _ptr(dx1.t), _ptr(dx2.t), _ptr(out.t)), "bk_d2f")
-    return out
+    return _into_similar(prob, "bk_d2f", x, pars, _ptr(dx1.t), _ptr(dx2.t))
 
 
 def dJdp(prob, x: HipVec, pars, ipar: int, dx: HipVec) -> HipVec:
     """dJ/dp(x) dx for params[ipar] (bk_djdp): the analytic value of dJvdp in _get_bordered_terms (:93-94)."""
-    ctx, out = prob.ctx, x.similar()
-    arr = (C.c_double * len(pars))(*pars)
-    ctx.check(ctx.lib.bk_djdp(prob.h, _ptr(x.t), arr, len(pars), int(ipar), _ptr(dx.t), _ptr(out.t)), "bk_djdp")
-    return out
+    return _into_similar(prob, "bk_djdp", x, pars, int(ipar), _ptr(dx.t))
 
 
 def fold_contract(prob, x: HipVec, pars, ipar: int, v: HipVec, w: HipVec, X=()):
     """One fused pass (bk_fold_contract): ([<w, d2F(x)[v, X_k]> for X_k in X], -<w, dJ/dp v>)."""
     ctx = prob.ctx
     m = len(X)
-    arr = (C.c_double * len(pars))(*pars)
-    xp = (C.c_void_p * max(m, 1))(*[t.t.data_ptr() for t in X])
+    xp = _vptrs(X)
     out = (C.c_double * (m + 1))()
-    ctx.check(ctx.lib.bk_fold_contract(prob.h, _ptr(x.t), arr, len(pars), int(ipar), _ptr(v.t), _ptr(w.t), m, xp, out),
+    ctx.check(ctx.lib.bk_fold_contract(prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), _ptr(v.t), _ptr(w.t), m, xp, out),
               "bk_fold_contract")
     return [out[k] for k in range(m)], out[m]
 
 
 def residual(prob, x: HipVec, pars) -> HipVec:
     """F(x, pars) with every parameter given (bk_residual)."""
-    ctx, out = prob.ctx, x.similar()
-    arr = (C.c_double * len(pars))(*pars)
-    ctx.check(ctx.lib.bk_residual(prob.h, _ptr(x.t), arr, len(pars), _ptr(out.t)), "bk_residual")
-    return out
+    return _into_similar(prob, "bk_residual", x, pars)
 
 
 def dpF(prob, x: HipVec, pars, ipar: int) -> HipVec:
     """Analytic dF/dp for params[ipar].  bk_residual_dparam evaluates ((p + eps) - p) / eps * phi_p(x) and phi_p does not
     depend on the parameters, so with p = 0 and eps = 1 the scalar is exactly 1."""
-    ctx, out = prob.ctx, x.similar()
     pv = list(pars)
     pv[ipar] = 0.0
-    arr = (C.c_double * len(pv))(*pv)
-    ctx.check(ctx.lib.bk_residual_dparam(prob.h, _ptr(x.t), arr, len(pv), int(ipar), 1.0, _ptr(out.t)), "bk_residual_dparam")
-    return out
+    return _into_similar(prob, "bk_residual_dparam", x, pv, int(ipar), 1.0)
 
 
 def _bls_opts(bls: BorderingBLS):
@@ -102,6 +116,174 @@ def _solve2(ls: _GMRES, J, rhs1: HipVec, rhs2: HipVec):
     ctx.check(ctx.lib.bk_gmres2(ctx.h, J.h, _ptr(rhs1.t), _ptr(rhs2.t), _ptr(x1.t), _ptr(x2.t), 0.0, 1.0, C.byref(o), ls._pl(),
                                 C.byref(cv), it), "bk_gmres2")
     return x1, x2, bool(cv.value), (it[0], it[1])
+
+
+# ------------------------------------------------------------------------------------------ what fold and Hopf share
+def _newton_minaug_mirror(point, step, norm, tol, max_iterations):
+    """_newton (src/Newton.jl:66-114) on G: ``point()`` -> (F, sigma, v, w) at the current unknowns, ``step(F, sigma, v, w)``
+    one update of them with the bordered vectors of that point.  Returns (last point, residuals, steps)."""
+    pt = point()
+    res = [norm(pt[0], pt[1])]
+    n = 0
+    while n < max_iterations and res[-1] > tol:
+        step(*pt)
+        pt = point()
+        res.append(norm(pt[0], pt[1]))
+        n += 1
+    return pt, res, n
+
+
+class _MinAugProblem:
+    """G(X, p2) = (F(x, p1), sigma) of a minimally augmented formulation with lens2: X = (x, scalar unknowns), p1 = the
+    problem's lens, parameter p2 = ``lens2``.  ``residual`` / ``jacobian`` / ``residual_dparam`` are the BifurcationProblem
+    surface continuation.newton_palc drives; the bordered vectors of a point are cached and solved once per point.  A
+    formulation supplies ``_p1`` (p1 of X), ``_solve_terms`` (v, w, sigma and the GMRES counts of the bordered solves), ``_vec``
+    (a residual vector from its x part and sigma), ``_sigma_p`` and ``update``."""
+
+    def __init__(self, prob, lens2: str, a, b, ls: _GMRES):
+        if lens2 == prob.lens:
+            raise ValueError(f"Please choose 2 different parameters. You only passed {lens2}")
+        self.prob, self.ctx = prob, prob.ctx
+        self.lens1, self.lens2 = prob.lens, lens2
+        self.ipar1, self.ipar2 = prob.param_names.index(prob.lens), prob.param_names.index(lens2)
+        self.ls = ls
+        self.a, self.b = a, b
+        self.delta = prob.delta
+        self.itlinear = 0                       # GMRES counts of the bordered-vector solves (the linear solver counts its own)
+        self._cache = None
+
+    def pvec(self, p1, p2):
+        return _params(self.prob, **{self.lens1: p1, self.lens2: p2})
+
+    def terms(self, X, p2: float):
+        """(v, w, sigma) of _compute_bordered_vectors at (X, p2), solved once per point."""
+        c = self._cache
+        if c is not None and np.array_equal(c[1], X.p) and c[2] == p2 and torch.equal(c[0].t, X.u.t):
+            return c[3]
+        v, w, sigma, *_, it = self._solve_terms(X, p2)      # fold_terms / hopf_terms: (v, w, sigma, ..., (itv, itw))
+        self.itlinear += it[0] + it[1]
+        t = (v, w, sigma)
+        self._cache = (X.u.copy(), np.array(X.p, dtype=np.float64), p2, t)
+        return t
+
+    def residual(self, X, p2: float):
+        _, _, sigma = self.terms(X, p2)
+        return self._vec(residual(self.prob, X.u, self.pvec(self._p1(X), p2)), sigma)
+
+    def residual_dparam(self, X, p2: float, eps=None):
+        """dG/dp2 = (dF/dp2, sigma_p2), analytic (the reference differentiates G by finite differences)."""
+        v, w, _ = self.terms(X, p2)
+        pv = self.pvec(self._p1(X), p2)
+        sp2 = self._sigma_p(X.u, pv, self.ipar2, v, w)
+        return self._vec(dpF(self.prob, X.u, pv, self.ipar2), sp2)
+
+    def jacobian(self, X, p2: float):
+        return _JacobianMinAug(self, X, p2)
+
+
+@dataclass
+class _JacobianMinAug:
+    """What jacobian(FoldMAProblem | HopfMAProblem, X, p2) hands to the linear solver: the point (no matrix)."""
+    ma: _MinAugProblem
+    X: object
+    p2: float
+
+
+def _linsolve_args(J: _JacobianMinAug, rhs):
+    """What bk_fold_linsolve and bk_hopf_linsolve take alike: (problem, v, w, params, nparams, outputs dX, pointers of the x
+    parts of ``rhs``, pointers of dX); v, w are the cached bordered vectors of the point."""
+    P = J.ma
+    v, w, _ = P.terms(J.X, J.p2)
+    pv = P.pvec(P._p1(J.X), J.p2)
+    dX = [J.X.u.similar() for _ in rhs]
+    return P, v, w, _carr(pv), len(pv), dX, _vptrs([r.u for r in rhs]), _vptrs(dX)
+
+
+class _MinAugLinearSolver:
+    """The linear solver of a minimally augmented problem; ``_run(J, [rhs...])`` -> (solutions, converged, GMRES iterations).
+    ``solve2`` serves both right-hand sides of the BorderingBLS BEC with ONE J \\ dpF solve: three GMRES solves where the
+    reference runs four."""
+
+    def __call__(self, J: _JacobianMinAug, rhs, a0=0.0, a1=1.0):
+        out, cv, it = self._run(J, [rhs])
+        return out[0], cv, it
+
+    def solve2(self, J: _JacobianMinAug, rhs1, rhs2, a0=0.0, a1=1.0):
+        out, cv, it = self._run(J, [rhs1, rhs2])
+        return out[0], out[1], cv, (it, 0)
+
+
+@dataclass
+class _MinAugBranch:
+    """What the records of continuation_fold and continuation_hopf share, one entry per point."""
+    p1: list = field(default_factory=list)
+    p2: list = field(default_factory=list)
+    ds: list = field(default_factory=list)
+    itnewton: list = field(default_factory=list)
+    itlinear: list = field(default_factory=list)
+    residuals: list = field(default_factory=list)
+    sol: list = field(default_factory=list)
+
+
+def _continuation_minaug(P: _MinAugProblem, lin: _MinAugLinearSolver, what: str, br: _MinAugBranch, guess, p2: float, cp, theta,
+                         normC, update_minaug_every_step, save_sol, ds_sequence, verbosity, record_x, skipped, describe,
+                         stop_after=None) -> bool:
+    """PALC on G(X, p2) with a Secant tangent through continuation.newton_palc and BorderingBLS(solver = lin, check_precision =
+    false): the two starting points of continuation (Continuation.jl:349-456) by newton on G, step-size control of
+    continuation.py or the prescribed ``ds_sequence``.  Every converged point goes into ``br``; its formulation's own fields by
+    ``record_x(X, val, tau)`` with val = P.update(...) (a, b renewed) or ``skipped(X)`` when update_minaug_every_step skips it.
+    The run ends when ``stop_after(val)`` holds, and True is returned then."""
+    def record(z, sol, ds_, val, tau):
+        record_x(z.u, val, tau)
+        br.p2.append(z.p); br.ds.append(ds_)
+        br.itnewton.append(sol.itnewton); br.itlinear.append(sol.itlineartot); br.residuals.append(list(sol.residuals))
+        if save_sol:
+            br.sol.append(z.copy())
+
+    nopt = Cn.NewtonPar(tol=cp.newton_options.tol, max_iterations=cp.newton_options.max_iterations, linsolver=lin)
+    bls = BorderingBLS(lin, check_precision=False)
+    sol0 = Cn.newton(P, guess, p2, nopt, normC)
+    if not sol0.converged:
+        raise RuntimeError(f"Newton failed to converge for the initial {what} guess")
+    ds = cp.ds if ds_sequence is None else ds_sequence[0]
+    p2b = p2 + ds / cp.eta
+    sol1 = Cn.newton(P, sol0.u, p2b, nopt, normC)
+    if not sol1.converged:
+        raise RuntimeError("Newton failed to converge. Required for the computation of the initial tangent")
+    z0, z1 = BorderedArray(sol0.u, p2), BorderedArray(sol1.u, p2b)
+    tau = Cn.secant_tangent(z1, z0, ds, theta)
+    z, z_old = z0.copy(), z0.copy()
+    record(z, sol0, ds, P.update(z.u, z.p), tau)
+    z_pred = z.copy().add_(tau, ds)
+    step = 0
+    while step < cp.max_steps and (cp.p_min < z.p < cp.p_max or step == 0):
+        it0 = P.itlinear
+        sol = Cn.newton_palc(P, z, tau, z_pred, ds, theta, bls, nopt, cp.p_min, cp.p_max, normC)
+        sol.itlineartot += P.itlinear - it0
+        if verbosity:
+            print(f"{what.lower()} step {step:3d} ds={ds:+.3e} p2={sol.u.p:+.8f} {describe(sol.u.u)} conv={sol.converged} "
+                  f"itnewton={sol.itnewton} itlinear={sol.itlineartot}")
+        if sol.converged:
+            z_old.copyto_(z)
+            z.copyto_(sol.u)
+            step += 1
+        if ds_sequence is not None:
+            if not sol.converged:
+                raise RuntimeError(f"{what} continuation step {step} did not converge with the prescribed ds")
+            ds_next, stop = (ds_sequence[step] if step < len(ds_sequence) else ds), step >= len(ds_sequence)
+        else:
+            ds_next, stop = Cn.step_size_control(ds, sol.converged, sol.itnewton, cp)
+        if sol.converged:
+            tau = Cn.secant_tangent(z, z_old, ds_next, theta)
+            val = P.update(z.u, z.p) if Cn.mod_counter(step, update_minaug_every_step) else skipped(z.u)
+            record(z, sol, ds, val, tau)
+            if stop_after is not None and stop_after(val):
+                return True
+        ds = ds_next
+        if stop:
+            break
+        z_pred = z.copy().add_(tau, ds)
+    return False
 
 
 # ------------------------------------------------------------------------------------------ fold point guesses
@@ -169,10 +351,8 @@ def newton_fold(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _GMRES, b
         F = prob.residual(x, p)
         return F, sigma, v, w
 
-    F, sigma, v, w = point()
-    res = [_norm_fold(F, sigma, norm_inf)]
-    step = 0
-    while step < max_iterations and res[-1] > tol:
+    def update(F, sigma, v, w):
+        nonlocal p, itlin, bad
         pars = prob._pvec(p)
         J = prob.jacobian(x, p)
         x1, x2, cv, it = _solve2(ls, J, F, dpF(prob, x, pars, ipar))
@@ -185,9 +365,9 @@ def newton_fold(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _GMRES, b
         dX = x1.copy().add_(x2, -dsig)
         x.add_(dX, -1.0)
         p -= dsig
-        F, sigma, v, w = point()
-        res.append(_norm_fold(F, sigma, norm_inf))
-        step += 1
+
+    (F, sigma, v, w), res, step = _newton_minaug_mirror(point, update, lambda F, sg: _norm_fold(F, sg, norm_inf), tol,
+                                                        max_iterations)
     return dict(u=BorderedArray(x, p), converged=res[-1] < tol, itnewton=step, itlineartot=itlin, residuals=res, v=v,
                 w=w.copy() if w is v else w, sigma=sigma, unconverged_solves=bad)
 
@@ -200,14 +380,13 @@ def newton_fold_native(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _G
     x = x0.copy()
     p = C.c_double(float(p0))
     pv = prob._pvec(p0)
-    arr = (C.c_double * len(pv))(*pv)
     v, w = x.similar(), x.similar()
     sigma = C.c_double()
     no = newton_opts(tol, max_iterations, norm_inf, callback=callback)
     bo, lo = _bls_opts(bls), ls._opts()
     res = L.NewtonResult()
     bad0 = ctx.get_option("fold_unconverged_solves")
-    ctx.check(ctx.lib.bk_newton_fold(ctx.h, prob.h, _ptr(x.t), C.byref(p), arr, len(pv), prob.ipar, _ptr(a.t), _ptr(b.t),
+    ctx.check(ctx.lib.bk_newton_fold(ctx.h, prob.h, _ptr(x.t), C.byref(p), _carr(pv), len(pv), prob.ipar, _ptr(a.t), _ptr(b.t),
                                      C.byref(no), C.byref(bo), C.byref(lo), ls._pl(), _ptr(v.t), _ptr(w.t), C.byref(sigma),
                                      C.byref(res)), "bk_newton_fold")
     return dict(u=BorderedArray(x, p.value), converged=bool(res.converged), itnewton=res.itnewton, itlineartot=res.itlinear,
@@ -216,62 +395,37 @@ def newton_fold_native(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _G
 
 
 # ------------------------------------------------------------------------------------------ the fold problem G(X, p2)
-class FoldProblem:
+def fold_terms(prob, x: HipVec, pars, ipar: int, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS):
+    """bk_fold_terms: (v, w, sigma, converged, (itv, itw)); w is v itself when ``a is b`` (J' = J: no second solve)."""
+    ctx = prob.ctx
+    v = x.similar()
+    w = v if a is b else x.similar()
+    sigma, cv = C.c_double(), C.c_int()
+    it = (C.c_int * 2)()
+    bo, lo = _bls_opts(bls), ls._opts()
+    ctx.check(ctx.lib.bk_fold_terms(ctx.h, prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), _ptr(a.t), _ptr(b.t),
+                                    C.byref(bo), C.byref(lo), ls._pl(), _ptr(v.t), _ptr(w.t), C.byref(sigma), None, C.byref(cv),
+                                    it), "bk_fold_terms")
+    return v, w, sigma.value, bool(cv.value), (it[0], it[1])
+
+
+class FoldProblem(_MinAugProblem):
     """FoldMinimallyAugmentedFormulation(prob, a, b, ...) + FoldMAProblem with lens2 (src/codim2/MinAugFold.jl,
-    continuation_fold :407-453): unknown X = BorderedArray(x, p1) (p1 = the problem's lens), parameter p2 = ``lens2``.
-    ``residual`` / ``jacobian`` / ``residual_dparam`` are the BifurcationProblem surface continuation.newton_palc drives;
-    the bordered vectors of a point are cached and solved once per point (bk_fold_terms)."""
+    continuation_fold :407-453): unknown X = BorderedArray(x, p1), the bordered vectors from bk_fold_terms."""
 
     def __init__(self, prob, lens2: str, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS | None = None):
-        if lens2 == prob.lens:
-            raise ValueError(f"Please choose 2 different parameters. You only passed {lens2}")
-        self.prob, self.ctx = prob, prob.ctx
-        self.lens1, self.lens2 = prob.lens, lens2
-        self.ipar1, self.ipar2 = prob.param_names.index(prob.lens), prob.param_names.index(lens2)
-        self.ls = ls
+        super().__init__(prob, lens2, a, b, ls)
         self.bls = bls if bls is not None else BorderingBLS(ls, check_precision=False)
-        self.a, self.b = a, b
-        self.delta = prob.delta
-        self.itlinear = 0                       # GMRES counts of the bordered-vector solves (the linear solver counts its own)
-        self._cache = None
 
-    def pvec(self, p1, p2):
-        return _params(self.prob, **{self.lens1: p1, self.lens2: p2})
+    _p1 = staticmethod(lambda X: X.p)
+    _vec = staticmethod(BorderedArray)
 
-    def terms(self, X: BorderedArray, p2: float):
-        """(v, w, sigma) of _compute_bordered_vectors at (X, p2), solved once per point."""
-        c = self._cache
-        if c is not None and c[1] == X.p and c[2] == p2 and torch.equal(c[0].t, X.u.t):
-            return c[3]
-        ctx = self.ctx
-        pv = self.pvec(X.p, p2)
-        arr = (C.c_double * len(pv))(*pv)
-        v = X.u.similar()
-        w = v if self.a is self.b else X.u.similar()
-        sigma, cv = C.c_double(), C.c_int()
-        it = (C.c_int * 2)()
-        bo, lo = _bls_opts(self.bls), self.ls._opts()
-        ctx.check(ctx.lib.bk_fold_terms(ctx.h, self.prob.h, _ptr(X.u.t), arr, len(pv), self.ipar1, _ptr(self.a.t),
-                                        _ptr(self.b.t), C.byref(bo), C.byref(lo), self.ls._pl(), _ptr(v.t), _ptr(w.t),
-                                        C.byref(sigma), None, C.byref(cv), it), "bk_fold_terms")
-        self.itlinear += it[0] + it[1]
-        t = (v, w, sigma.value)
-        self._cache = (X.u.copy(), X.p, p2, t)
-        return t
+    def _solve_terms(self, X: BorderedArray, p2: float):
+        return fold_terms(self.prob, X.u, self.pvec(X.p, p2), self.ipar1, self.a, self.b, self.ls, self.bls)
 
-    def residual(self, X: BorderedArray, p2: float) -> BorderedArray:
-        _, _, sigma = self.terms(X, p2)
-        return BorderedArray(residual(self.prob, X.u, self.pvec(X.p, p2)), sigma)
-
-    def residual_dparam(self, X: BorderedArray, p2: float, eps=None) -> BorderedArray:
-        """dG/dp2 = (dF/dp2, -<w, dJ/dp2 v>), analytic (the reference differentiates G by finite differences)."""
-        v, w, _ = self.terms(X, p2)
-        pv = self.pvec(X.p, p2)
-        _, sp2 = fold_contract(self.prob, X.u, pv, self.ipar2, v, w)
-        return BorderedArray(dpF(self.prob, X.u, pv, self.ipar2), sp2)
-
-    def jacobian(self, X: BorderedArray, p2: float):
-        return JacobianFold(self, X, p2)
+    def _sigma_p(self, x, pv, ipar, v, w):
+        """-<w, dJ/dp v>"""
+        return fold_contract(self.prob, x, pv, ipar, v, w)[1]
 
     def update(self, X: BorderedArray, p2: float):
         """update!(probma, iter, state) (:280-313) after a converged step: a = w/|w|, b = v/|v| from the bordered vectors of the
@@ -286,64 +440,34 @@ class FoldProblem:
         return bt
 
 
-@dataclass
-class JacobianFold:
-    """What jacobian(FoldMAProblem, X, p2) hands to FoldLinearSolverMinAug: the point (no matrix)."""
-    fold: FoldProblem
-    X: BorderedArray
-    p2: float
+class FoldLinearSolverMinAug(_MinAugLinearSolver):
+    """FoldLinearSolverMinAug (:168-178) -> foldMALinearSolver, usehessian branch (:146-164) as bk_fold_linsolve."""
 
-
-class FoldLinearSolverMinAug:
-    """FoldLinearSolverMinAug (:168-178) -> foldMALinearSolver, usehessian branch (:146-164) as bk_fold_linsolve.
-    ``solve2`` serves both right-hand sides of the BorderingBLS BEC with ONE J \\ dpF solve: three GMRES solves where the
-    reference runs four."""
-
-    def _run(self, Jf: JacobianFold, rhs):
-        F = Jf.fold
-        v, w, _ = F.terms(Jf.X, Jf.p2)
-        ctx = F.ctx
-        pv = F.pvec(Jf.X.p, Jf.p2)
-        arr = (C.c_double * len(pv))(*pv)
-        m = len(rhs)
-        dX = [Jf.X.u.similar() for _ in range(m)]
-        ru = (C.c_void_p * m)(*[r.u.t.data_ptr() for r in rhs])
+    def _run(self, J: _JacobianMinAug, rhs):
+        F, v, w, arr, npar, dX, ru, dxp = _linsolve_args(J, rhs)
+        ctx, m = F.ctx, len(rhs)
         rp = (C.c_double * m)(*[float(r.p) for r in rhs])
-        dxp = (C.c_void_p * m)(*[d.t.data_ptr() for d in dX])
         ds = (C.c_double * m)()
         cv, it = C.c_int(), C.c_int()
         lo = F.ls._opts()
-        ctx.check(ctx.lib.bk_fold_linsolve(ctx.h, F.prob.h, _ptr(Jf.X.u.t), arr, len(pv), F.ipar1, _ptr(v.t), _ptr(w.t), m,
-                                           ru, rp, C.byref(lo), F.ls._pl(), dxp, ds, C.byref(cv), C.byref(it)),
-                  "bk_fold_linsolve")
+        ctx.check(ctx.lib.bk_fold_linsolve(ctx.h, F.prob.h, _ptr(J.X.u.t), arr, npar, F.ipar1, _ptr(v.t), _ptr(w.t), m, ru, rp,
+                                           C.byref(lo), F.ls._pl(), dxp, ds, C.byref(cv), C.byref(it)), "bk_fold_linsolve")
         return [BorderedArray(dX[k], ds[k]) for k in range(m)], bool(cv.value), it.value
 
-    def __call__(self, Jf: JacobianFold, rhs: BorderedArray, a0=0.0, a1=1.0):
-        out, cv, it = self._run(Jf, [rhs])
-        return out[0], cv, it
 
-    def solve2(self, Jf: JacobianFold, rhs1: BorderedArray, rhs2: BorderedArray, a0=0.0, a1=1.0):
-        out, cv, it = self._run(Jf, [rhs1, rhs2])
-        return out[0], out[1], cv, (it, 0)
+JacobianFold = _JacobianMinAug
 
 
 # ------------------------------------------------------------------------------------------ continuation_fold
 @dataclass
-class FoldBranch:
+class FoldBranch(_MinAugBranch):
     """The record of continuation_fold (record_from_solution, :330-346): p1 (lens1), p2 (lens2), BT, CP per point."""
-    p1: list = field(default_factory=list)
-    p2: list = field(default_factory=list)
     BT: list = field(default_factory=list)
     CP: list = field(default_factory=list)
-    ds: list = field(default_factory=list)
-    itnewton: list = field(default_factory=list)
-    itlinear: list = field(default_factory=list)
-    residuals: list = field(default_factory=list)
-    sol: list = field(default_factory=list)
 
 
 def _norminf_fold(z):
-    return max(z.u.norminf(), abs(z.p))
+    return _nanmax(z.u.norminf(), abs(z.p))
 
 
 def continuation_fold(prob, fold_guess: BorderedArray, p2: float, lens2: str, a: HipVec, b: HipVec, ls: _GMRES,
@@ -355,58 +479,14 @@ def continuation_fold(prob, fold_guess: BorderedArray, p2: float, lens2: str, a:
     continuation (Continuation.jl:349-456) by newton on G, step-size control of continuation.py.  After every converged step a, b
     are updated (update_minaug_every_step = 1) and BT, CP recorded.  ``ds_sequence`` (optional) replaces the step-size control by
     a fixed list of steps (comparisons with a restatement).  Codim-2 points are not located."""
-    F = FoldProblem(prob, lens2, a, b, ls)
-    lin = FoldLinearSolverMinAug()
-    nopt = Cn.NewtonPar(tol=cp.newton_options.tol, max_iterations=cp.newton_options.max_iterations, linsolver=lin)
-    bls = BorderingBLS(lin, check_precision=False)
-    normC = _norminf_fold if norm_inf else (lambda z: z.norm())
     br = FoldBranch()
-    sol0 = Cn.newton(F, fold_guess, p2, nopt, normC)
-    if not sol0.converged:
-        raise RuntimeError("Newton failed to converge for the initial fold guess")
-    ds = cp.ds if ds_sequence is None else ds_sequence[0]
-    p2b = p2 + ds / cp.eta
-    sol1 = Cn.newton(F, sol0.u, p2b, nopt, normC)
-    if not sol1.converged:
-        raise RuntimeError("Newton failed to converge. Required for the computation of the initial tangent")
-    z0, z1 = BorderedArray(sol0.u, p2), BorderedArray(sol1.u, p2b)
 
-    def record(z, sol, ds_, bt, cpv):
-        br.p1.append(z.u.p); br.p2.append(z.p); br.BT.append(bt); br.CP.append(cpv); br.ds.append(ds_)
-        br.itnewton.append(sol.itnewton); br.itlinear.append(sol.itlineartot); br.residuals.append(list(sol.residuals))
-        if save_sol:
-            br.sol.append(z.copy())
+    def record_x(X, bt, tau):
+        br.p1.append(X.p); br.BT.append(bt); br.CP.append(tau.p)
 
-    tau = Cn.secant_tangent(z1, z0, ds, theta)
-    z, z_old = z0.copy(), z0.copy()
-    record(z, sol0, ds, F.update(z.u, z.p), tau.p)
-    z_pred = z.copy().add_(tau, ds)
-    step = 0
-    while step < cp.max_steps and (cp.p_min < z.p < cp.p_max or step == 0):
-        it0 = F.itlinear
-        sol = Cn.newton_palc(F, z, tau, z_pred, ds, theta, bls, nopt, cp.p_min, cp.p_max, normC)
-        sol.itlineartot += F.itlinear - it0
-        if verbosity:
-            print(f"fold step {step:3d} ds={ds:+.3e} p2={sol.u.p:+.8f} p1={sol.u.u.p:+.8f} conv={sol.converged} "
-                  f"itnewton={sol.itnewton} itlinear={sol.itlineartot}")
-        if sol.converged:
-            z_old.copyto_(z)
-            z.copyto_(sol.u)
-            step += 1
-        if ds_sequence is not None:
-            if not sol.converged:
-                raise RuntimeError(f"fold continuation step {step} did not converge with the prescribed ds")
-            ds_next, stop = (ds_sequence[step] if step < len(ds_sequence) else ds), step >= len(ds_sequence)
-        else:
-            ds_next, stop = Cn.step_size_control(ds, sol.converged, sol.itnewton, cp)
-        if sol.converged:
-            tau = Cn.secant_tangent(z, z_old, ds_next, theta)
-            bt = F.update(z.u, z.p) if Cn.mod_counter(step, update_minaug_every_step) else float("nan")
-            record(z, sol, ds, bt, tau.p)
-        ds = ds_next
-        if stop:
-            break
-        z_pred = z.copy().add_(tau, ds)
+    _continuation_minaug(FoldProblem(prob, lens2, a, b, ls), FoldLinearSolverMinAug(), "fold", br, fold_guess, p2, cp, theta,
+                         _norminf_fold if norm_inf else (lambda z: z.norm()), update_minaug_every_step, save_sol, ds_sequence,
+                         verbosity, record_x, skipped=lambda X: float("nan"), describe=lambda X: f"p1={X.p:+.8f}")
     return br
 
 
@@ -469,12 +549,6 @@ class HopfVec:
         return len(self.u) + 2
 
 
-def _nanmax(*vals):
-    """max that propagates a NaN from any argument (Python's max drops it depending on the argument order)."""
-    vals = [float(v) for v in vals]
-    return math.nan if any(v != v for v in vals) else max(vals)
-
-
 def _cptr(z):
     return _ptr(z.t) if z is not None else None
 
@@ -502,29 +576,22 @@ def _cscale(z, c: complex):
 
 def hopf_d2F(prob, x: HipVec, pars, dx1: HipVec, dx2: HipVec) -> HipVec:
     """d2F(x)[dx1, dx2] of CGL2d for real dx1, dx2 (bk_hopf_d2f)."""
-    ctx, out = prob.ctx, x.similar()
-    arr = (C.c_double * len(pars))(*pars)
-    ctx.check(ctx.lib.bk_hopf_d2f(prob.h, _ptr(x.t), arr, len(pars), _ptr(dx1.t), _ptr(dx2.t), _ptr(out.t)), "bk_hopf_d2f")
-    return out
+    return _into_similar(prob, "bk_hopf_d2f", x, pars, _ptr(dx1.t), _ptr(dx2.t))
 
 
 def hopf_dJdp(prob, x: HipVec, pars, ipar: int, dx: HipVec) -> HipVec:
     """dJ/dp(x) dx of CGL2d for params[ipar] (bk_hopf_djdp)."""
-    ctx, out = prob.ctx, x.similar()
-    arr = (C.c_double * len(pars))(*pars)
-    ctx.check(ctx.lib.bk_hopf_djdp(prob.h, _ptr(x.t), arr, len(pars), int(ipar), _ptr(dx.t), _ptr(out.t)), "bk_hopf_djdp")
-    return out
+    return _into_similar(prob, "bk_hopf_djdp", x, pars, int(ipar), _ptr(dx.t))
 
 
 def hopf_contract(prob, x: HipVec, pars, ipar: int, v, w, X=()):
     """One fused pass (bk_hopf_contract): ([w^H d2F(x)[v, X_k] for X_k in X], w^H dJ/dp v, w^H v) as complex numbers."""
     ctx = prob.ctx
     m = len(X)
-    arr = (C.c_double * len(pars))(*pars)
-    xp = (C.c_void_p * max(m, 1))(*[t.t.data_ptr() for t in X])
+    xp = _vptrs(X)
     out = (C.c_double * (2 * (m + 2)))()
-    ctx.check(ctx.lib.bk_hopf_contract(prob.h, _ptr(x.t), arr, len(pars), int(ipar), _ptr(v[0].t), _ptr(v[1].t), _ptr(w[0].t),
-                                       _ptr(w[1].t), m, xp, out), "bk_hopf_contract")
+    ctx.check(ctx.lib.bk_hopf_contract(prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), _ptr(v[0].t), _ptr(v[1].t),
+                                       _ptr(w[0].t), _ptr(w[1].t), m, xp, out), "bk_hopf_contract")
     z = [complex(out[2 * k], out[2 * k + 1]) for k in range(m + 2)]
     return z[:m], z[m], z[m + 1]
 
@@ -532,15 +599,14 @@ def hopf_contract(prob, x: HipVec, pars, ipar: int, v, w, X=()):
 def hopf_terms(prob, x: HipVec, pars, ipar: int, omega: float, a, b, ls: _GMRES):
     """bk_hopf_terms: (v, w, sigma, sigma_p, sigma_omega, converged, (itv, itw)); v, w as (re, im) pairs."""
     ctx = prob.ctx
-    arr = (C.c_double * len(pars))(*pars)
     vr, vi, wr, wi = x.similar(), x.similar(), x.similar(), x.similar()
     sg, spp, sw = (C.c_double * 2)(), (C.c_double * 2)(), (C.c_double * 2)()
     cv = C.c_int()
     it = (C.c_int * 2)()
     lo = ls._opts()
-    ctx.check(ctx.lib.bk_hopf_terms(ctx.h, prob.h, _ptr(x.t), arr, len(pars), int(ipar), float(omega), _cptr(a[0]), _cptr(a[1]),
-                                    _cptr(b[0]), _cptr(b[1]), C.byref(lo), ls._pl(), _ptr(vr.t), _ptr(vi.t), _ptr(wr.t),
-                                    _ptr(wi.t), sg, spp, sw, C.byref(cv), it), "bk_hopf_terms")
+    ctx.check(ctx.lib.bk_hopf_terms(ctx.h, prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), float(omega), _cptr(a[0]),
+                                    _cptr(a[1]), _cptr(b[0]), _cptr(b[1]), C.byref(lo), ls._pl(), _ptr(vr.t), _ptr(vi.t),
+                                    _ptr(wr.t), _ptr(wi.t), sg, spp, sw, C.byref(cv), it), "bk_hopf_terms")
     return ((vr, vi), (wr, wi), complex(sg[0], sg[1]), complex(spp[0], spp[1]), complex(sw[0], sw[1]), bool(cv.value),
             (it[0], it[1]))
 
@@ -636,10 +702,8 @@ def newton_hopf(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=2
         bad += 0 if (cv and cv2) else 1
         return prob.residual(x, p), sigma, v, w
 
-    F, sigma, v, w = point()
-    res = [_norm_hopf(F, sigma, norm_inf)]
-    step = 0
-    while step < max_iterations and res[-1] > tol:
+    def update(F, sigma, v, w):
+        nonlocal p, om, itlin, bad
         pars = prob._pvec(p)
         J = prob.jacobian(x, p)
         x1, x2, cv, it = _solve2(ls, J, F, dpF(prob, x, pars, ipar))
@@ -651,9 +715,9 @@ def newton_hopf(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=2
         x.add_(x1, -1.0)
         p -= dp
         om -= dw
-        F, sigma, v, w = point()
-        res.append(_norm_hopf(F, sigma, norm_inf))
-        step += 1
+
+    (F, sigma, v, w), res, step = _newton_minaug_mirror(point, update, lambda F, sg: _norm_hopf(F, sg, norm_inf), tol,
+                                                        max_iterations)
     return dict(u=HopfVec(x, [p, om]), converged=res[-1] < tol, itnewton=step, itlineartot=itlin, residuals=res, v=v, w=w,
                 sigma=sigma, unconverged_solves=bad)
 
@@ -664,16 +728,15 @@ def newton_hopf_native(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_itera
     x = X0.u.copy()
     p, om = C.c_double(float(X0.p[0])), C.c_double(float(X0.p[1]))
     pv = prob._pvec(p.value)
-    arr = (C.c_double * len(pv))(*pv)
     vr, vi, wr, wi = x.similar(), x.similar(), x.similar(), x.similar()
     sigma = (C.c_double * 2)()
     no = newton_opts(tol, max_iterations, norm_inf, callback=callback)
     lo = ls._opts()
     res = L.NewtonResult()
     bad0 = ctx.get_option("hopf_unconverged_solves")
-    ctx.check(ctx.lib.bk_newton_hopf(ctx.h, prob.h, _ptr(x.t), C.byref(p), C.byref(om), arr, len(pv), prob.ipar, _cptr(a[0]),
-                                     _cptr(a[1]), _cptr(b[0]), _cptr(b[1]), C.byref(no), C.byref(lo), ls._pl(), _ptr(vr.t),
-                                     _ptr(vi.t), _ptr(wr.t), _ptr(wi.t), sigma, C.byref(res)), "bk_newton_hopf")
+    ctx.check(ctx.lib.bk_newton_hopf(ctx.h, prob.h, _ptr(x.t), C.byref(p), C.byref(om), _carr(pv), len(pv), prob.ipar,
+                                     _cptr(a[0]), _cptr(a[1]), _cptr(b[0]), _cptr(b[1]), C.byref(no), C.byref(lo), ls._pl(),
+                                     _ptr(vr.t), _ptr(vi.t), _ptr(wr.t), _ptr(wi.t), sigma, C.byref(res)), "bk_newton_hopf")
     return dict(u=HopfVec(x, [p.value, om.value]), converged=bool(res.converged), itnewton=res.itnewton,
                 itlineartot=res.itlinear, residuals=[res.residuals[i] for i in range(res.itnewton + 1)], v=(vr, vi), w=(wr, wi),
                 sigma=complex(sigma[0], sigma[1]),
@@ -681,50 +744,19 @@ def newton_hopf_native(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_itera
 
 
 # ------------------------------------------------------------------------------------------ the Hopf problem G(X, p2)
-class HopfProblem:
-    """HopfMinimallyAugmentedFormulation(prob, a, b, ...) + HopfMAProblem with lens2: unknown X = HopfVec(x, [p1, omega]),
-    parameter p2 = ``lens2``.  ``residual`` / ``jacobian`` / ``residual_dparam`` are the surface continuation.newton_palc
-    drives; the bordered vectors of a point are solved once per point (bk_hopf_terms)."""
+class HopfProblem(_MinAugProblem):
+    """HopfMinimallyAugmentedFormulation(prob, a, b, ...) + HopfMAProblem with lens2: unknown X = HopfVec(x, [p1, omega]), a, b,
+    v, w complex (re, im) pairs, the bordered vectors from bk_hopf_terms."""
 
-    def __init__(self, prob, lens2: str, a, b, ls: _GMRES):
-        if lens2 == prob.lens:
-            raise ValueError(f"Please choose 2 different parameters. You only passed {lens2}")
-        self.prob, self.ctx = prob, prob.ctx
-        self.lens1, self.lens2 = prob.lens, lens2
-        self.ipar1, self.ipar2 = prob.param_names.index(prob.lens), prob.param_names.index(lens2)
-        self.ls = ls
-        self.a, self.b = a, b
-        self.delta = prob.delta
-        self.itlinear = 0
-        self._cache = None
+    _p1 = staticmethod(lambda X: X.p[0])
+    _vec = staticmethod(lambda u, s: HopfVec(u, [s.real, s.imag]))
 
-    def pvec(self, p1, p2):
-        return _params(self.prob, **{self.lens1: p1, self.lens2: p2})
+    def _solve_terms(self, X: HopfVec, p2: float):
+        return hopf_terms(self.prob, X.u, self.pvec(X.p[0], p2), self.ipar1, X.p[1], self.a, self.b, self.ls)
 
-    def terms(self, X: HopfVec, p2: float):
-        """(v, w, sigma) at (X, p2), solved once per point."""
-        c = self._cache
-        if c is not None and np.array_equal(c[1], X.p) and c[2] == p2 and torch.equal(c[0].t, X.u.t):
-            return c[3]
-        v, w, sigma, _, _, _, it = hopf_terms(self.prob, X.u, self.pvec(X.p[0], p2), self.ipar1, X.p[1], self.a, self.b, self.ls)
-        self.itlinear += it[0] + it[1]
-        t = (v, w, sigma)
-        self._cache = (X.u.copy(), X.p.copy(), p2, t)
-        return t
-
-    def residual(self, X: HopfVec, p2: float) -> HopfVec:
-        _, _, sigma = self.terms(X, p2)
-        return HopfVec(residual(self.prob, X.u, self.pvec(X.p[0], p2)), [sigma.real, sigma.imag])
-
-    def residual_dparam(self, X: HopfVec, p2: float, eps=None) -> HopfVec:
-        """dG/dp2 = (dF/dp2, sigma_p2) with sigma_p2 = -w^H dJ/dp2 v, analytic."""
-        v, w, _ = self.terms(X, p2)
-        pv = self.pvec(X.p[0], p2)
-        _, P, _ = hopf_contract(self.prob, X.u, pv, self.ipar2, v, w)
-        return HopfVec(dpF(self.prob, X.u, pv, self.ipar2), [-P.real, -P.imag])
-
-    def jacobian(self, X: HopfVec, p2: float):
-        return JacobianHopf(self, X, p2)
+    def _sigma_p(self, x, pv, ipar, v, w):
+        """-w^H dJ/dp v"""
+        return -hopf_contract(self.prob, x, pv, ipar, v, w)[1]
 
     def update(self, X: HopfVec, p2: float):
         """update!(probma, iter, state) after a converged step: a = w/|w|, b = v/|v| from the bordered vectors of the new
@@ -735,59 +767,31 @@ class HopfProblem:
         return float(X.p[1])
 
 
-@dataclass
-class JacobianHopf:
-    """What jacobian(HopfMAProblem, X, p2) hands to HopfLinearSolverMinAug: the point (no matrix)."""
-    hopf: HopfProblem
-    X: HopfVec
-    p2: float
+class HopfLinearSolverMinAug(_MinAugLinearSolver):
+    """HopfLinearSolverMinAug -> _hopf_MA_linear_solver, usehessian branch, as bk_hopf_linsolve (real GMRES solves)."""
 
-
-class HopfLinearSolverMinAug:
-    """HopfLinearSolverMinAug -> _hopf_MA_linear_solver, usehessian branch, as bk_hopf_linsolve.  ``solve2`` serves both
-    right-hand sides of the BorderingBLS BEC with ONE J \\ dpF solve: three real GMRES solves where the reference runs four."""
-
-    def _run(self, Jh: JacobianHopf, rhs):
-        H = Jh.hopf
-        v, w, _ = H.terms(Jh.X, Jh.p2)
-        ctx = H.ctx
-        pv = H.pvec(Jh.X.p[0], Jh.p2)
-        arr = (C.c_double * len(pv))(*pv)
-        m = len(rhs)
-        dX = [Jh.X.u.similar() for _ in range(m)]
-        ru = (C.c_void_p * m)(*[r.u.t.data_ptr() for r in rhs])
+    def _run(self, J: _JacobianMinAug, rhs):
+        H, v, w, arr, npar, dX, ru, dxp = _linsolve_args(J, rhs)
+        ctx, m = H.ctx, len(rhs)
         rp = (C.c_double * (2 * m))(*[float(c) for r in rhs for c in r.p])
-        dxp = (C.c_void_p * m)(*[d.t.data_ptr() for d in dX])
         ds = (C.c_double * (2 * m))()
         cv, it = C.c_int(), C.c_int()
         lo = H.ls._opts()
-        ctx.check(ctx.lib.bk_hopf_linsolve(ctx.h, H.prob.h, _ptr(Jh.X.u.t), arr, len(pv), H.ipar1, _ptr(v[0].t), _ptr(v[1].t),
+        ctx.check(ctx.lib.bk_hopf_linsolve(ctx.h, H.prob.h, _ptr(J.X.u.t), arr, npar, H.ipar1, _ptr(v[0].t), _ptr(v[1].t),
                                            _ptr(w[0].t), _ptr(w[1].t), m, ru, rp, C.byref(lo), H.ls._pl(), dxp, ds,
                                            C.byref(cv), C.byref(it)), "bk_hopf_linsolve")
         return [HopfVec(dX[k], [ds[2 * k], ds[2 * k + 1]]) for k in range(m)], bool(cv.value), it.value
 
-    def __call__(self, Jh: JacobianHopf, rhs: HopfVec, a0=0.0, a1=1.0):
-        out, cv, it = self._run(Jh, [rhs])
-        return out[0], cv, it
 
-    def solve2(self, Jh: JacobianHopf, rhs1: HopfVec, rhs2: HopfVec, a0=0.0, a1=1.0):
-        out, cv, it = self._run(Jh, [rhs1, rhs2])
-        return out[0], out[1], cv, (it, 0)
+JacobianHopf = _JacobianMinAug
 
 
 # ------------------------------------------------------------------------------------------ continuation_hopf
 @dataclass
-class HopfBranch:
+class HopfBranch(_MinAugBranch):
     """The record of continuation_hopf (record_from_solution): p1 (lens1), p2 (lens2), omega and BT = omega per point."""
-    p1: list = field(default_factory=list)
-    p2: list = field(default_factory=list)
     omega: list = field(default_factory=list)
     BT: list = field(default_factory=list)
-    ds: list = field(default_factory=list)
-    itnewton: list = field(default_factory=list)
-    itlinear: list = field(default_factory=list)
-    residuals: list = field(default_factory=list)
-    sol: list = field(default_factory=list)
     stopped_at_bt: bool = False
 
 
@@ -799,60 +803,15 @@ def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls
     continuation.py.  After every converged step a, b are updated (update!) and the run stops once |omega| < 100 tol
     (threshBT: the curve is near a Bogdanov-Takens point).  ``ds_sequence`` (optional) replaces the step-size control by a fixed
     list of steps.  Codim-2 points are not located."""
-    H = HopfProblem(prob, lens2, a, b, ls)
-    lin = HopfLinearSolverMinAug()
-    nopt = Cn.NewtonPar(tol=cp.newton_options.tol, max_iterations=cp.newton_options.max_iterations, linsolver=lin)
-    bls = BorderingBLS(lin, check_precision=False)
-    normC = (lambda z: z.norminf()) if norm_inf else (lambda z: z.norm())
-    thresh_bt = 100 * cp.newton_options.tol
     br = HopfBranch()
-    sol0 = Cn.newton(H, hopf_guess, p2, nopt, normC)
-    if not sol0.converged:
-        raise RuntimeError("Newton failed to converge for the initial Hopf guess")
-    ds = cp.ds if ds_sequence is None else ds_sequence[0]
-    p2b = p2 + ds / cp.eta
-    sol1 = Cn.newton(H, sol0.u, p2b, nopt, normC)
-    if not sol1.converged:
-        raise RuntimeError("Newton failed to converge. Required for the computation of the initial tangent")
-    z0, z1 = BorderedArray(sol0.u, p2), BorderedArray(sol1.u, p2b)
 
-    def record(z, sol, ds_, om):
-        br.p1.append(float(z.u.p[0])); br.p2.append(z.p); br.omega.append(float(z.u.p[1])); br.BT.append(om); br.ds.append(ds_)
-        br.itnewton.append(sol.itnewton); br.itlinear.append(sol.itlineartot); br.residuals.append(list(sol.residuals))
-        if save_sol:
-            br.sol.append(z.copy())
+    def record_x(X, om, tau):
+        br.p1.append(float(X.p[0])); br.omega.append(float(X.p[1])); br.BT.append(om)
 
-    tau = Cn.secant_tangent(z1, z0, ds, theta)
-    z, z_old = z0.copy(), z0.copy()
-    record(z, sol0, ds, H.update(z.u, z.p))
-    z_pred = z.copy().add_(tau, ds)
-    step = 0
-    while step < cp.max_steps and (cp.p_min < z.p < cp.p_max or step == 0):
-        it0 = H.itlinear
-        sol = Cn.newton_palc(H, z, tau, z_pred, ds, theta, bls, nopt, cp.p_min, cp.p_max, normC)
-        sol.itlineartot += H.itlinear - it0
-        if verbosity:
-            print(f"hopf step {step:3d} ds={ds:+.3e} p2={sol.u.p:+.8f} p1={sol.u.u.p[0]:+.8f} omega={sol.u.u.p[1]:+.8f} "
-                  f"conv={sol.converged} itnewton={sol.itnewton} itlinear={sol.itlineartot}")
-        if sol.converged:
-            z_old.copyto_(z)
-            z.copyto_(sol.u)
-            step += 1
-        if ds_sequence is not None:
-            if not sol.converged:
-                raise RuntimeError(f"Hopf continuation step {step} did not converge with the prescribed ds")
-            ds_next, stop = (ds_sequence[step] if step < len(ds_sequence) else ds), step >= len(ds_sequence)
-        else:
-            ds_next, stop = Cn.step_size_control(ds, sol.converged, sol.itnewton, cp)
-        if sol.converged:
-            tau = Cn.secant_tangent(z, z_old, ds_next, theta)
-            om = H.update(z.u, z.p) if Cn.mod_counter(step, update_minaug_every_step) else float(z.u.p[1])
-            record(z, sol, ds, om)
-            if abs(om) < thresh_bt:
-                br.stopped_at_bt = True
-                break
-        ds = ds_next
-        if stop:
-            break
-        z_pred = z.copy().add_(tau, ds)
+    thresh_bt = 100 * cp.newton_options.tol
+    br.stopped_at_bt = _continuation_minaug(
+        HopfProblem(prob, lens2, a, b, ls), HopfLinearSolverMinAug(), "Hopf", br, hopf_guess, p2, cp, theta,
+        (lambda z: z.norminf()) if norm_inf else (lambda z: z.norm()), update_minaug_every_step, save_sol, ds_sequence,
+        verbosity, record_x, skipped=lambda X: float(X.p[1]), describe=lambda X: f"p1={X.p[0]:+.8f} omega={X.p[1]:+.8f}",
+        stop_after=lambda om: abs(om) < thresh_bt)
     return br

@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "minaug.h"
 #include "ops.h"
 #include "stream.h"
 
@@ -94,18 +95,7 @@ __global__ void __launch_bounds__(kThreads) fold_contract_kernel(size_t n, const
             elem(pu[i], pv[i], pw[i], xa);
         }
     }
-    __shared__ double sm[M + 1][4];
-    const int lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k <= M; ++k) {
-        const double t = wave_sum(s[k]);
-        if (lane == 0) sm[k][wv_] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x <= M) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * (M + 1) + k] = (sm[k][0] + sm[k][1]) + (sm[k][2] + sm[k][3]);
-    }
+    block_sum_store<M + 1>(s, partials);
 }
 
 static int v_fold_pw(bk_ctx* ctx, size_t n, const double* u, const double c[4], const double* x1, const double* x2, double* out) {
@@ -130,19 +120,10 @@ static int v_fold_contract(bk_ctx* ctx, size_t n, const double* u, const double*
     const int grid = grid_for(n, vec ? 4 : 1, kRedBlocks);        // stream_loop<2>: 2 x 16 B per lane per chunk
     {
         ProfScope ps(ctx, "fold_contract", 8.0 * n * (3 + m));
-#define BK_FC(M)                                                                                                                                     \
-    do {                                                                                                                                             \
-        if (nth) hipLaunchKernelGGL((fold_contract_kernel<M, 2, true>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, u, v, w, x[0], x[1], x[2], P, ctx->d_partials); \
-        else if (vec) hipLaunchKernelGGL((fold_contract_kernel<M, 2, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, u, v, w, x[0], x[1], x[2], P, ctx->d_partials); \
-        else hipLaunchKernelGGL((fold_contract_kernel<M, 1, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, u, v, w, x[0], x[1], x[2], P, ctx->d_partials); \
-    } while (0)
-        switch (m) {
-            case 0: BK_FC(0); break;
-            case 1: BK_FC(1); break;
-            case 2: BK_FC(2); break;
-            default: BK_FC(3); break;
-        }
-#undef BK_FC
+        contract_dispatch(m, vec, nth, [&](auto M, auto V, auto NT) {
+            hipLaunchKernelGGL((fold_contract_kernel<decltype(M)::value, decltype(V)::value, decltype(NT)::value>), dim3(grid),
+                               dim3(kThreads), 0, ctx->stream, n, u, v, w, x[0], x[1], x[2], P, ctx->d_partials);
+        });
         BK_HIP(ctx, hipGetLastError());
     }
     BK_TRY(reduce_finish(ctx, grid, m + 1, 0));
@@ -214,41 +195,15 @@ int fold_linsolve(bk_ctx* ctx, bk_problem* prob, bk_op* J, const double* x, cons
     double h[4], g[4];
     BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
     WsGuard ws(ctx);
-    double *dpF = nullptr, *x2 = nullptr;
-    BK_TRY(ws.get(n, &dpF));
-    BK_TRY(ws.get(n, &x2));
-    BK_TRY(pde_dparam(ctx, prob->desc.pde, ipar, n, 1.0, x, dpF));           // analytic dpF (:88-89)
-    GmresResult r0, r1, r2;
-    BK_TRY(linsolve2(ctx, J, rhsu[0], dX[0], dpF, x2, 0.0, 1.0, lo, pl, &r0, &r2));
-    int c = r0.converged & r2.converged, its = r0.niter + r2.niter;
-    if (nrhs == 2) {
-        BK_TRY(linsolve(ctx, J, rhsu[1], dX[1], 0.0, 1.0, lo, pl, &r1));
-        c &= r1.converged;
-        its += r1.niter;
-    }
-    const double* X[3] = {dX[0], nrhs == 2 ? dX[1] : x2, x2};
+    MinAugSolves S;
+    BK_TRY(minaug_solves(ctx, prob, J, x, ipar, nrhs, rhsu, lo, pl, dX, ws, &S));           // analytic dpF (:88-89)
     double s[4];
-    BK_TRY(v_fold_contract(ctx, n, x, v, w, nrhs + 1, X, h, g, s));
+    BK_TRY(v_fold_contract(ctx, n, x, v, w, nrhs + 1, S.X, h, g, s));
     const double sx2 = -s[nrhs], sp = -s[nrhs + 1];
-    for (int k = 0; k < nrhs; ++k) {
-        dsig[k] = (rhsp[k] - (-s[k])) / (sp - sx2);
-        BK_TRY(v_axpby(ctx, n, -dsig[k], x2, 1.0, dX[k]));
-    }
-    *cv = c;
-    *itlinear = its;
-    return 0;
-}
-
-// callback(state; fromNewton) as solver.hip's newton_cb: the built-in cbMaxNorm veto first, then the user's function
-int fold_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear, double p) {
-    if (no->max_residual > 0.0 && !(residual < no->max_residual)) return 0;
-    if (no->callback) return no->callback(no->callback_user, x, fx, residual, step, itlinear, p, nullptr, NAN, 1) != 0;
-    return 1;
-}
-
-int check_common(bk_ctx* ctx, bk_problem* prob) {
-    if (prob->ctx != ctx) return set_error(ctx, "fold: the problem belongs to another context");
-    return 0;
+    for (int k = 0; k < nrhs; ++k) dsig[k] = (rhsp[k] - (-s[k])) / (sp - sx2);
+    *cv = S.converged;
+    *itlinear = S.niter;
+    return minaug_update(ctx, n, S, nrhs, dsig, 1, dX);
 }
 
 }  // namespace
@@ -292,7 +247,7 @@ int bk_fold_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* 
                   const double* a, const double* b, const bk_bordering_opts* bopts, const bk_gmres_opts* lsopts,
                   bk_precond* pl, double* v, double* w, double* sigma, double* sigma_p, int* converged, int itlinear[2]) {
     if (!ctx || !prob || !x || !params || !a || !b || !bopts || !lsopts || !v || !w || !sigma) return -1;
-    BK_TRY(check_common(ctx, prob));
+    BK_TRY(minaug_check(ctx, prob, "fold"));
     double h[4], g[4];
     BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
     if (v == a || v == b || w == a || w == b) return set_error(ctx, "bk_fold_terms: v and w must not alias a or b");
@@ -301,12 +256,12 @@ int bk_fold_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* 
     WsGuard ws(ctx);
     double* zero = nullptr;
     BK_TRY(ws.get(n, &zero));
-    bk_op* J = nullptr;
-    BK_TRY(bk_jacobian(prob, x, params, nparams, &J));
     int cv = 0, it[2] = {0, 0};
-    int s = fold_terms(ctx, J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it);
-    bk_op_destroy(J);
-    BK_TRY(s);
+    {
+        JPair jp;
+        BK_TRY(jp.make(prob, x, params, nparams));
+        BK_TRY(fold_terms(ctx, jp.J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it));
+    }
     if (sigma_p) {
         double t[1];
         BK_TRY(v_fold_contract(ctx, n, x, v, w, 0, nullptr, h, g, t));
@@ -322,20 +277,12 @@ int bk_fold_linsolve(bk_ctx* ctx, bk_problem* prob, const double* x, const doubl
                      const bk_gmres_opts* lsopts, bk_precond* pl, double* const* dX, double* dsigma, int* converged,
                      int* itlinear) {
     if (!ctx || !prob || !x || !params || !v || !w || !rhsu || !rhsp || !lsopts || !dX || !dsigma) return -1;
-    BK_TRY(check_common(ctx, prob));
-    if (nrhs < 1 || nrhs > 2) return set_error(ctx, "bk_fold_linsolve: 1 or 2 right-hand sides (got %d)", nrhs);
-    for (int k = 0; k < nrhs; ++k) {
-        if (!rhsu[k] || !dX[k]) return -1;
-        for (int j = 0; j < nrhs; ++j)
-            if (dX[k] == rhsu[j]) return set_error(ctx, "bk_fold_linsolve: dX must not alias a right-hand side");
-    }
-    if (nrhs == 2 && dX[0] == dX[1]) return set_error(ctx, "bk_fold_linsolve: dX[0] and dX[1] must be distinct");
-    bk_op* J = nullptr;
-    BK_TRY(bk_jacobian(prob, x, params, nparams, &J));
+    BK_TRY(minaug_check(ctx, prob, "fold"));
+    BK_TRY(minaug_check_rhs(ctx, "bk_fold_linsolve", nrhs, rhsu, dX));
+    JPair jp;
+    BK_TRY(jp.make(prob, x, params, nparams));
     int cv = 0, it = 0;
-    int s = fold_linsolve(ctx, prob, J, x, params, nparams, ipar, v, w, nrhs, rhsu, rhsp, *lsopts, pl, dX, dsigma, &cv, &it);
-    bk_op_destroy(J);
-    BK_TRY(s);
+    BK_TRY(fold_linsolve(ctx, prob, jp.J, x, params, nparams, ipar, v, w, nrhs, rhsu, rhsp, *lsopts, pl, dX, dsigma, &cv, &it));
     if (converged) *converged = cv;
     if (itlinear) *itlinear = it;
     return 0;
@@ -345,7 +292,7 @@ int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
                    const double* a, const double* b, const bk_newton_opts* no, const bk_bordering_opts* bopts,
                    const bk_gmres_opts* lsopts, bk_precond* pl, double* v, double* w, double* sigma, bk_newton_result* res) {
     if (!ctx || !prob || !x || !p || !params || !a || !b || !no || !bopts || !lsopts || !v || !w || !sigma || !res) return -1;
-    BK_TRY(check_common(ctx, prob));
+    BK_TRY(minaug_check(ctx, prob, "fold"));
     if (no->max_iterations > BK_MAX_NEWTON_ITER) return set_error(ctx, "max_iterations > %d", BK_MAX_NEWTON_ITER);
     double h[4], g[4];
     BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
@@ -362,53 +309,40 @@ int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
     double par[BK_MAX_PARAMS];
     for (int i = 0; i < nparams; ++i) par[i] = params[i];
     double pc = *p;
-    int itlin = 0;
     // one evaluation of the fold residual (:16-38) at (x, pc): F, and sigma with the bordered vectors v, w of this point, which
     // the Newton step at the same point reuses (the reference solves them again in _get_bordered_terms, :71-99)
-    auto point = [&](double* r) -> int {
+    auto point = [&](double* r, int* itl) -> int {
         par[ipar] = pc;
-        bk_op* J = nullptr;
-        BK_TRY(bk_jacobian(prob, x, par, nparams, &J));
         int cv = 0, it[2] = {0, 0};
-        int s = fold_terms(ctx, J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it);
-        bk_op_destroy(J);
-        BK_TRY(s);
-        itlin += it[0] + it[1];
+        {
+            JPair jp;
+            BK_TRY(jp.make(prob, x, par, nparams));
+            BK_TRY(fold_terms(ctx, jp.J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it));
+        }
+        *itl = it[0] + it[1];
         if (!cv) ctx->diag.fold_unconverged += 1.0;
         BK_TRY(bk_residual(prob, x, par, nparams, fx));
         return norm_fold(ctx, n, fx, *sigma, inf, r);
     };
-    double r;
-    BK_TRY(point(&r));
-    int step = 0;
-    res->residuals[0] = r;
-    int compute = fold_cb(no, x, fx, r, 0, 0, pc);
-    while (step < no->max_iterations && r > no->tol && compute) {
-        // Newton step: J_fold [dX; dsig] = [F; sigma] with foldMALinearSolver (:119-166), x -= dX, p -= dsig (src/Newton.jl:97)
+    // Newton step: J_fold [dX; dsig] = [F; sigma] with foldMALinearSolver (:119-166), x -= dX, p -= dsig (src/Newton.jl:97)
+    auto step = [&](int* itl) -> int {
         par[ipar] = pc;
-        bk_op* J = nullptr;
-        BK_TRY(bk_jacobian(prob, x, par, nparams, &J));
         const double* rhsu[1] = {fx};
         double* dXs[1] = {dX};
         double rhsp[1] = {*sigma}, dsig[1] = {0.0};
-        int cv = 0, it = 0;
-        int s = fold_linsolve(ctx, prob, J, x, par, nparams, ipar, v, w, 1, rhsu, rhsp, *lsopts, pl, dXs, dsig, &cv, &it);
-        bk_op_destroy(J);
-        BK_TRY(s);
-        itlin += it;
+        int cv = 0;
+        {
+            JPair jp;
+            BK_TRY(jp.make(prob, x, par, nparams));
+            BK_TRY(fold_linsolve(ctx, prob, jp.J, x, par, nparams, ipar, v, w, 1, rhsu, rhsp, *lsopts, pl, dXs, dsig, &cv, itl));
+        }
         if (!cv) ctx->diag.fold_unconverged += 1.0;
         BK_TRY(v_axpby(ctx, n, -1.0, dX, 1.0, x));
         pc -= dsig[0];
-        const int before = itlin;
-        BK_TRY(point(&r));
-        step += 1;
-        res->residuals[step] = r;
-        compute = fold_cb(no, x, fx, r, step, it + (itlin - before), pc);
-    }
+        return 0;
+    };
+    BK_TRY(minaug_newton(no, res, x, fx, &pc, point, step));
     *p = pc;
-    res->converged = (res->residuals[step] < no->tol) & fold_cb(no, x, fx, r, step, 0, pc);
-    res->itnewton = step;
-    res->itlinear = itlin;
     return 0;
 }
 

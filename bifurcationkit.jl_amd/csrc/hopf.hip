@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "minaug.h"
 #include "ops.h"
 #include "stream.h"
 
@@ -148,18 +149,7 @@ __global__ void __launch_bounds__(kThreads) hopf_contract_kernel(size_t N, HopfS
                  xa1, xa2);
         }
     }
-    __shared__ double sm[NV][4];
-    const int lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const double t = wave_sum(s[k]);
-        if (lane == 0) sm[k][wv_] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * NV + k] = (sm[k][0] + sm[k][1]) + (sm[k][2] + sm[k][3]);
-    }
+    block_sum_store<NV>(s, partials);
 }
 
 static int v_hopf_pw(bk_ctx* ctx, size_t n, const double* u, const CglCoef& c, const double* x1, const double* x2, double* out) {
@@ -184,19 +174,10 @@ static int v_hopf_contract(bk_ctx* ctx, size_t n, const double* u, const double*
     const int grid = grid_for(N, vec ? 2 : 1, kRedBlocks);
     {
         ProfScope ps(ctx, "hopf_contract", 8.0 * n * (5 + m));
-#define BK_HC(M)                                                                                                                        \
-    do {                                                                                                                                \
-        if (nth) hipLaunchKernelGGL((hopf_contract_kernel<M, 2, true>), dim3(grid), dim3(kThreads), 0, ctx->stream, N, S, c, ctx->d_partials); \
-        else if (vec) hipLaunchKernelGGL((hopf_contract_kernel<M, 2, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, N, S, c, ctx->d_partials); \
-        else hipLaunchKernelGGL((hopf_contract_kernel<M, 1, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, N, S, c, ctx->d_partials); \
-    } while (0)
-        switch (m) {
-            case 0: BK_HC(0); break;
-            case 1: BK_HC(1); break;
-            case 2: BK_HC(2); break;
-            default: BK_HC(3); break;
-        }
-#undef BK_HC
+        contract_dispatch(m, vec, nth, [&](auto M, auto V, auto NT) {
+            hipLaunchKernelGGL((hopf_contract_kernel<decltype(M)::value, decltype(V)::value, decltype(NT)::value>), dim3(grid),
+                               dim3(kThreads), 0, ctx->stream, N, S, c, ctx->d_partials);
+        });
         BK_HIP(ctx, hipGetLastError());
     }
     const int nv = 2 * (m + 2);
@@ -265,21 +246,10 @@ int hopf_linsolve(bk_ctx* ctx, bk_problem* prob, bk_op* J, const double* x, cons
     CglCoef c;
     BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));
     WsGuard ws(ctx);
-    double *dpF = nullptr, *x2 = nullptr;
-    BK_TRY(ws.get(n, &dpF));
-    BK_TRY(ws.get(n, &x2));
-    BK_TRY(pde_dparam(ctx, prob->desc.pde, c.ipar, n / 2, 1.0, x, dpF));           // analytic dpF
-    GmresResult r0, r1, r2;
-    BK_TRY(linsolve2(ctx, J, rhsu[0], dX[0], dpF, x2, 0.0, 1.0, lo, pl, &r0, &r2));
-    int cvv = r0.converged & r2.converged, its = r0.niter + r2.niter;
-    if (nrhs == 2) {
-        BK_TRY(linsolve(ctx, J, rhsu[1], dX[1], 0.0, 1.0, lo, pl, &r1));
-        cvv &= r1.converged;
-        its += r1.niter;
-    }
-    const double* X[3] = {dX[0], nrhs == 2 ? dX[1] : x2, x2};
+    MinAugSolves S;
+    BK_TRY(minaug_solves(ctx, prob, J, x, c.ipar, nrhs, rhsu, lo, pl, dX, ws, &S));           // analytic dpF
     double s[10];
-    BK_TRY(v_hopf_contract(ctx, n, x, vr, vi, wr, wi, nrhs + 1, X, c, s));
+    BK_TRY(v_hopf_contract(ctx, n, x, vr, vi, wr, wi, nrhs + 1, S.X, c, s));
     const int m = nrhs + 1;
     const double s2r = s[2 * nrhs], s2i = s[2 * nrhs + 1];
     const double spr = -s[2 * m], spi = -s[2 * m + 1];                  // sigma_p = -P
@@ -292,34 +262,11 @@ int hopf_linsolve(bk_ctx* ctx, bk_problem* prob, bk_op* J, const double* x, cons
         const double dp = (b1 * a22 - a12 * b2) / det, dw = (a11 * b2 - a21 * b1) / det;
         dpw[2 * k] = dp;
         dpw[2 * k + 1] = dw;
-        BK_TRY(v_axpby(ctx, n, -dp, x2, 1.0, dX[k]));
     }
-    *cv = cvv;
-    *itlinear = its;
-    return 0;
+    *cv = S.converged;
+    *itlinear = S.niter;
+    return minaug_update(ctx, n, S, nrhs, dpw, 2, dX);
 }
-
-int hopf_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear, double p) {
-    if (no->max_residual > 0.0 && !(residual < no->max_residual)) return 0;
-    if (no->callback) return no->callback(no->callback_user, x, fx, residual, step, itlinear, p, nullptr, NAN, 1) != 0;
-    return 1;
-}
-
-int hopf_check(bk_ctx* ctx, bk_problem* prob) {
-    if (prob->ctx != ctx) return set_error(ctx, "hopf: the problem belongs to another context");
-    return 0;
-}
-
-// the Jacobian and its adjoint at (x, params); both destroyed by the guard
-struct JPair {
-    bk_op* J = nullptr;
-    bk_op* Jt = nullptr;
-    ~JPair() { if (J) bk_op_destroy(J); if (Jt) bk_op_destroy(Jt); }
-    int make(bk_problem* prob, const double* x, const double* par, int np) {
-        BK_TRY(bk_jacobian(prob, x, par, np, &J));
-        return bk_jacobian_adjoint(prob, x, par, np, &Jt);
-    }
-};
 
 }  // namespace
 }  // namespace bk
@@ -359,7 +306,7 @@ int bk_hopf_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* 
                   bk_precond* pl, double* v_re, double* v_im, double* w_re, double* w_im, double sigma[2], double sigma_p[2],
                   double sigma_omega[2], int* converged, int itlinear[2]) {
     if (!ctx || !prob || !x || !params || !a_re || !b_re || !lsopts || !v_re || !v_im || !w_re || !w_im || !sigma) return -1;
-    BK_TRY(hopf_check(ctx, prob));
+    BK_TRY(minaug_check(ctx, prob, "hopf"));
     CglCoef c;
     BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));
     const double* outs[4] = {v_re, v_im, w_re, w_im};
@@ -377,7 +324,7 @@ int bk_hopf_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* 
     int cv = 0, it[2] = {0, 0};
     {
         JPair jp;
-        BK_TRY(jp.make(prob, x, params, nparams));
+        BK_TRY(jp.make(prob, x, params, nparams, true));
         BK_TRY(hopf_terms(ctx, jp.J, jp.Jt, n, omega, a_re, a_im, b_re, b_im, *lsopts, pl, zero, v_re, v_im, w_re, w_im, sigma,
                           &cv, it));
     }
@@ -397,23 +344,15 @@ int bk_hopf_linsolve(bk_ctx* ctx, bk_problem* prob, const double* x, const doubl
                      const double* const* rhsu, const double* rhspw, const bk_gmres_opts* lsopts, bk_precond* pl,
                      double* const* dX, double* dpw, int* converged, int* itlinear) {
     if (!ctx || !prob || !x || !params || !v_re || !v_im || !w_re || !w_im || !rhsu || !rhspw || !lsopts || !dX || !dpw) return -1;
-    BK_TRY(hopf_check(ctx, prob));
+    BK_TRY(minaug_check(ctx, prob, "hopf"));
     CglCoef c;
     BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));                // validates the problem kind and parameters up front
-    if (nrhs < 1 || nrhs > 2) return set_error(ctx, "bk_hopf_linsolve: 1 or 2 right-hand sides (got %d)", nrhs);
-    for (int k = 0; k < nrhs; ++k) {
-        if (!rhsu[k] || !dX[k]) return -1;
-        for (int j = 0; j < nrhs; ++j)
-            if (dX[k] == rhsu[j]) return set_error(ctx, "bk_hopf_linsolve: dX must not alias a right-hand side");
-    }
-    if (nrhs == 2 && dX[0] == dX[1]) return set_error(ctx, "bk_hopf_linsolve: dX[0] and dX[1] must be distinct");
-    bk_op* J = nullptr;
-    BK_TRY(bk_jacobian(prob, x, params, nparams, &J));
+    BK_TRY(minaug_check_rhs(ctx, "bk_hopf_linsolve", nrhs, rhsu, dX));
+    JPair jp;
+    BK_TRY(jp.make(prob, x, params, nparams));
     int cv = 0, it = 0;
-    int s = hopf_linsolve(ctx, prob, J, x, params, nparams, ipar, v_re, v_im, w_re, w_im, nrhs, rhsu, rhspw, *lsopts, pl, dX,
-                          dpw, &cv, &it);
-    bk_op_destroy(J);
-    BK_TRY(s);
+    BK_TRY(hopf_linsolve(ctx, prob, jp.J, x, params, nparams, ipar, v_re, v_im, w_re, w_im, nrhs, rhsu, rhspw, *lsopts, pl, dX,
+                         dpw, &cv, &it));
     if (converged) *converged = cv;
     if (itlinear) *itlinear = it;
     return 0;
@@ -426,7 +365,7 @@ int bk_newton_hopf(bk_ctx* ctx, bk_problem* prob, double* x, double* p, double* 
     if (!ctx || !prob || !x || !p || !omega || !params || !a_re || !b_re || !no || !lsopts || !v_re || !v_im || !w_re || !w_im ||
         !sigma || !res)
         return -1;
-    BK_TRY(hopf_check(ctx, prob));
+    BK_TRY(minaug_check(ctx, prob, "hopf"));
     if (no->max_iterations > BK_MAX_NEWTON_ITER) return set_error(ctx, "max_iterations > %d", BK_MAX_NEWTON_ITER);
     CglCoef c;
     BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));                // validates the problem kind and parameters up front
@@ -448,58 +387,45 @@ int bk_newton_hopf(bk_ctx* ctx, bk_problem* prob, double* x, double* p, double* 
     double par[BK_MAX_PARAMS];
     for (int i = 0; i < nparams; ++i) par[i] = params[i];
     double pc = *p, wc = *omega;
-    int itlin = 0;
     // one evaluation of the Hopf residual (:22-45) at (x, pc, wc), with the bordered vectors v, w of this point, which the
     // Newton step at the same point reuses (the reference solves them again in _get_bordered_terms)
-    auto point = [&](double* r) -> int {
+    auto point = [&](double* r, int* itl) -> int {
         par[ipar] = pc;
         int cv = 0, it[2] = {0, 0};
         {
             JPair jp;
-            BK_TRY(jp.make(prob, x, par, nparams));
+            BK_TRY(jp.make(prob, x, par, nparams, true));
             BK_TRY(hopf_terms(ctx, jp.J, jp.Jt, n, wc, a_re, a_im, b_re, b_im, *lsopts, pl, zero, v_re, v_im, w_re, w_im, sigma,
                               &cv, it));
         }
-        itlin += it[0] + it[1];
+        *itl = it[0] + it[1];
         if (!cv) ctx->diag.hopf_unconverged += 1.0;
         BK_TRY(bk_residual(prob, x, par, nparams, fx));
         return norm_hopf(ctx, n, fx, sigma, inf, r);
     };
-    double r;
-    BK_TRY(point(&r));
-    int step = 0;
-    res->residuals[0] = r;
-    int compute = hopf_cb(no, x, fx, r, 0, 0, pc);
-    while (step < no->max_iterations && r > no->tol && compute) {
-        // Newton step: J_hopf [dX; dp; domega] = [F; Re sigma; Im sigma] (HopfLinearSolverMinAug), x -= dX, (p, omega) -= (dp, domega)
+    // Newton step: J_hopf [dX; dp; domega] = [F; Re sigma; Im sigma] (HopfLinearSolverMinAug), x -= dX, (p, omega) -= (dp, domega)
+    auto step = [&](int* itl) -> int {
         par[ipar] = pc;
-        bk_op* J = nullptr;
-        BK_TRY(bk_jacobian(prob, x, par, nparams, &J));
         const double* rhsu[1] = {fx};
         double* dXs[1] = {dX};
         double dpw[2] = {0.0, 0.0};
-        int cv = 0, it = 0;
-        // the coefficients of d2F and dJ/dp follow the current parameter value (par), not the caller's params
-        int s = hopf_linsolve(ctx, prob, J, x, par, nparams, ipar, v_re, v_im, w_re, w_im, 1, rhsu, sigma, *lsopts, pl, dXs, dpw,
-                              &cv, &it);
-        bk_op_destroy(J);
-        BK_TRY(s);
-        itlin += it;
+        int cv = 0;
+        {
+            // the coefficients of d2F and dJ/dp follow the current parameter value (par), not the caller's params
+            JPair jp;
+            BK_TRY(jp.make(prob, x, par, nparams));
+            BK_TRY(hopf_linsolve(ctx, prob, jp.J, x, par, nparams, ipar, v_re, v_im, w_re, w_im, 1, rhsu, sigma, *lsopts, pl, dXs,
+                                 dpw, &cv, itl));
+        }
         if (!cv) ctx->diag.hopf_unconverged += 1.0;
         BK_TRY(v_axpby(ctx, n, -1.0, dX, 1.0, x));
         pc -= dpw[0];
         wc -= dpw[1];
-        const int before = itlin;
-        BK_TRY(point(&r));
-        step += 1;
-        res->residuals[step] = r;
-        compute = hopf_cb(no, x, fx, r, step, it + (itlin - before), pc);
-    }
+        return 0;
+    };
+    BK_TRY(minaug_newton(no, res, x, fx, &pc, point, step));
     *p = pc;
     *omega = wc;
-    res->converged = (res->residuals[step] < no->tol) & hopf_cb(no, x, fx, r, step, 0, pc);
-    res->itnewton = step;
-    res->itlinear = itlin;
     return 0;
 }
 

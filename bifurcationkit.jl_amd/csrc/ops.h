@@ -262,5 +262,9 @@ int linsolve2(bk_ctx* ctx, bk_op* J, const double* rhs1, double* x1, const doubl
 int bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R, double nn,
                   double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_bordering_opts& bo,
                   const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2]);
+// callback(state; fromNewton) of the Newton correctors (solver.hip, minaug.h): the cbMaxNorm veto, then the user's function;
+// 0 = stop
+int newton_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear, double p,
+              const double* z0u, double z0p, int from_newton);
 
 }  // namespace bk

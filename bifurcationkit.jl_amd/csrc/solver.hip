@@ -1459,17 +1459,17 @@ static int norm_of(bk_ctx* ctx, size_t n, const double* x, bool inf, double* out
     return inf ? v_nrminf(ctx, n, x, out) : v_nrm2(ctx, n, x, out);
 }
 
-}  // namespace bk
-
-extern "C" {
-
 // callback(state; fromNewton): the built-in cbMaxNorm veto first, then the user's function pointer
-static int newton_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear,
-                     double p, const double* z0u, double z0p, int from_newton) {
+int newton_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear,
+              double p, const double* z0u, double z0p, int from_newton) {
     if (no->max_residual > 0.0 && !(residual < no->max_residual)) return 0;      // cbMaxNorm, src/Newton.jl:156-159
     if (no->callback) return no->callback(no->callback_user, x, fx, residual, step, itlinear, p, z0u, z0p, from_newton) != 0;
     return 1;
 }
+
+}  // namespace bk
+
+extern "C" {
 
 int bk_newton(bk_ctx* ctx, bk_problem* prob, double* x, const double* params, int nparams, const bk_newton_opts* no,
               const bk_gmres_opts* lsopts, bk_precond* pl, bk_newton_result* res) {

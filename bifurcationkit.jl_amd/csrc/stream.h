@@ -1,5 +1,6 @@
-// Streaming scaffolding of the HBM-bound kernels (vecops.hip, fold.hip): 256-thread workgroups, 16-byte loads per lane, the
-// contiguous-burst grid-stride walk and the wave64 sum.  Internal header.
+// Streaming scaffolding of the HBM-bound kernels (vecops.hip, fold.hip, hopf.hip, and minaug.h for the epilogue the last two
+// share): 256-thread workgroups, 16-byte loads per lane, the contiguous-burst grid-stride walk and the wave64 sum.
+// Internal header.
 #pragma once
 #include <cstdint>
 #include <type_traits>

@@ -129,3 +129,28 @@ def test_hessian_formulas_match_central_differences_of_the_oracle_jacobian(kind,
         Fp = (op.F(u, *[pars[k] + (eps if k == name else 0) for k in names]) -
               op.F(u, *[pars[k] - (eps if k == name else 0) for k in names])) / (2 * eps)
         assert np.abs(Fp - m.dFdp(u, pars, name)).max() <= 1e-7 * np.abs(Fp).max(), name
+
+
+def test_fold_max_norm_propagates_nan():
+    """normN(BorderedArray(F, sigma)) in the max norm is NaN when F or sigma is NaN, whatever its position (norm_fold of
+    fold.hip); for finite input it is the plain max."""
+    from bk_amd import codim2
+
+    class F:
+        def __init__(self, v, p=None):
+            self.v, self.u, self.p = v, self, p
+
+        def norminf(self):
+            return self.v
+
+        def norm(self):
+            return self.v
+
+    nan = float("nan")
+    for f, sg in ((1.0, nan), (nan, 2.0), (0.0, nan), (nan, nan)):
+        assert codim2._norm_fold(F(f), sg, True) != codim2._norm_fold(F(f), sg, True), (f, sg)
+        assert codim2._norm_fold(F(f), sg, False) != codim2._norm_fold(F(f), sg, False), (f, sg)
+        assert codim2._norminf_fold(F(f, sg)) != codim2._norminf_fold(F(f, sg)), (f, sg)
+    assert codim2._norm_fold(F(1.0), -3.0, True) == 3.0 and codim2._norm_fold(F(4.0), -3.0, True) == 4.0
+    assert codim2._norm_fold(F(4.0), -3.0, False) == 5.0
+    assert codim2._norminf_fold(F(1.0, -3.0)) == 3.0 and codim2._norminf_fold(F(4.0, -3.0)) == 4.0
