@@ -196,6 +196,12 @@ SIGNATURES = {
                              VP, C.POINTER(VP), c_double_p, c_int_p, c_int_p]),
     "bk_newton_hopf": (I, [VP, VP, VP, c_double_p, c_double_p, c_double_p, I, I, VP, VP, VP, VP, C.POINTER(NewtonOpts),
                            C.POINTER(GmresOpts), VP, VP, VP, VP, VP, c_double_p, C.POINTER(NewtonResult)]),
+    "bk_hopf_d3f": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP]),
+    "bk_hopf_nf_rhs": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP, VP]),
+    "bk_hopf_nf_contract": (I, [VP, VP, c_double_p, I, I, VP, VP, VP, VP, VP, VP, VP, VP, c_double_p]),
+    "bk_hopf_normal_form": (I, [VP, VP, VP, c_double_p, I, I, D, VP, VP, VP, VP, C.POINTER(GmresOpts), VP, VP, VP, VP, VP,
+                                c_double_p, c_int_p, c_int_p]),
+    "bk_hopf_orbit": (I, [VP, SZ, VP, VP, VP, VP, VP, VP, VP, D, D, I, c_double_p, C.POINTER(VP)]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 """Fold and Hopf points: refinement and two-parameter continuation with the minimally augmented formulations of
-src/codim2/MinAugFold.jl and MinAugHopf.jl (Hopf: the second half of this module), matrix-free on the preconditioned GMRES
+src/codim2/MinAugFold.jl and MinAugHopf.jl (Hopf: the second half of this module; the Hopf normal form and the periodic-orbit
+predictor of src/NormalForms.jl: its last section), matrix-free on the preconditioned GMRES
 path (the reference assembles the systems for MatrixBLS / MinAugMatrixBased, which cannot run at the sizes of this library).
 
   FoldProblem              FoldMinimallyAugmentedFormulation + FoldMAProblem: G(X, p2) = (F(x, p1), sigma(x, p1)), X = (x, p1)
@@ -815,3 +816,208 @@ def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls
         verbosity, record_x, skipped=lambda X: float(X.p[1]), describe=lambda X: f"p1={X.p[0]:+.8f} omega={X.p[1]:+.8f}",
         stop_after=lambda om: abs(om) < thresh_bt)
     return br
+
+
+# ================================================================================================== Hopf normal form
+# __hopf_normal_form (src/NormalForms.jl:1009-1076) and predictor(::Hopf, ds) (:1227-1281) for CGL2d, matrix-free:
+#
+#   hopf_d3F, hopf_nf_rhs, hopf_nf_contract, hopf_orbit   the device passes (bk_hopf_d3f, bk_hopf_nf_rhs, bk_hopf_nf_contract,
+#                                                         bk_hopf_orbit)
+#   hopf_eigenpair            zeta, zeta* from the null vectors v, w of a newton_hopf result, |zeta| = 1, <zeta, zeta*> = 1
+#   hopf_normal_form          the computation call by call on the plugin surface (ls(J, rhs1, rhs2), ls.solve_complex)
+#   hopf_normal_form_native   the same as one library call (bk_hopf_normal_form)
+#   get_normal_form           get_normal_form(br, ind) for a Hopf point of a native branch: refine, then the normal form
+#   predictor                 the second-order guess of the periodic orbit that branches off
+#
+# z' = z (i omega + a dp + b |z|^2); inner(x, y) = sum conj(x) y = cinner(x, y), so a = cinner(av, zeta*), b = cinner(bv, zeta*).
+# dpF and dJ/dp are analytic where the reference differentiates (ForwardDiff / central differences).
+@dataclass
+class HopfNormalForm:
+    """HopfNormalForm(a, b, Psi110, Psi001, Psi200) (src/NormalForms.jl:1066); Psi200 is a (re, im) pair."""
+    a: complex | None = None
+    b: complex | None = None
+    Psi110: object = None
+    Psi001: object = None
+    Psi200: object = None
+
+
+@dataclass
+class Hopf:
+    """The reference's Hopf record (x0, p, omega, zeta, zeta_star, nf, type; params and lens as there) plus what the solves
+    reported: ``converged`` (all three), ``itlinear`` (GMRES counts of the Psi001, Psi110, Psi200 solves) and, from the native
+    call, ``unconverged_solves``."""
+    x0: object
+    p: float
+    omega: float
+    zeta: object
+    zeta_star: object
+    nf: HopfNormalForm = field(default_factory=HopfNormalForm)
+    type: str = "?"
+    params: list | None = None
+    lens: str | None = None
+    converged: bool | None = None
+    itlinear: tuple = ()
+    unconverged_solves: int | None = None
+
+
+def hopf_type(b: complex) -> str:
+    """:1067-1073"""
+    return "SuperCritical" if b.real < 0 else ("SubCritical" if b.real > 0 else "Singular")
+
+
+def hopf_d3F(prob, x: HipVec, pars, dx1: HipVec, dx2: HipVec, dx3: HipVec) -> HipVec:
+    """d3F(x)[dx1, dx2, dx3] of CGL2d for real arguments (bk_hopf_d3f)."""
+    return _into_similar(prob, "bk_hopf_d3f", x, pars, _ptr(dx1.t), _ptr(dx2.t), _ptr(dx3.t))
+
+
+def hopf_nf_rhs(prob, x: HipVec, pars, zeta):
+    """One fused pass (bk_hopf_nf_rhs): (d2F[zeta, zeta] / 2 as a (re, im) pair, d2F[zeta, conj zeta])."""
+    ctx = prob.ctx
+    rr, ri, r11 = x.similar(), x.similar(), x.similar()
+    ctx.check(ctx.lib.bk_hopf_nf_rhs(prob.h, _ptr(x.t), _carr(pars), len(pars), _ptr(zeta[0].t), _ptr(zeta[1].t), _ptr(rr.t),
+                                     _ptr(ri.t), _ptr(r11.t)), "bk_hopf_nf_rhs")
+    return (rr, ri), r11
+
+
+def hopf_nf_contract(prob, x: HipVec, pars, ipar: int, zeta, zeta_star, Psi001: HipVec, Psi110: HipVec, Psi200):
+    """One fused pass (bk_hopf_nf_contract): the coefficients (a, b) as complex numbers."""
+    ctx = prob.ctx
+    out = (C.c_double * 4)()
+    ctx.check(ctx.lib.bk_hopf_nf_contract(prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), _ptr(zeta[0].t), _ptr(zeta[1].t),
+                                          _ptr(zeta_star[0].t), _ptr(zeta_star[1].t), _ptr(Psi001.t), _ptr(Psi110.t),
+                                          _ptr(Psi200[0].t), _ptr(Psi200[1].t), out), "bk_hopf_nf_contract")
+    return complex(out[0], out[1]), complex(out[2], out[3])
+
+
+def hopf_orbit(x0: HipVec, zeta, Psi001: HipVec, Psi110: HipVec, Psi200, ds: float, amp: float, ts):
+    """[x0 + 2 Re(zeta A) + ds Psi001 + |A|^2 Psi110 + 2 Re(A^2 Psi200) for A = amp e^{i t}, t in ts] (bk_hopf_orbit: eight
+    phases per pass over the inputs)."""
+    ctx = x0.ctx
+    ts = [float(t) for t in ts]
+    outs = [x0.similar() for _ in ts]
+    ctx.check(ctx.lib.bk_hopf_orbit(ctx.h, x0.n, _ptr(x0.t), _ptr(zeta[0].t), _ptr(zeta[1].t), _ptr(Psi001.t), _ptr(Psi110.t),
+                                    _ptr(Psi200[0].t), _ptr(Psi200[1].t), float(ds), float(amp), len(ts),
+                                    (C.c_double * max(len(ts), 1))(*ts), _vptrs(outs)), "bk_hopf_orbit")
+    return outs
+
+
+def hopf_eigenpair(prob, sol):
+    """(zeta, zeta*) of the normal form from a newton_hopf / newton_hopf_native result: its v spans ker(J - i omega) and its w
+    ker(J' + i omega) (the start_with_eigen = Val(false) branch, :1173-1179).  zeta = v / |v|, zeta* = w / cinner(zeta, w), so that
+    cinner(zeta, zeta_star) == 1; cinner(x, y) = x^H y conjugates its FIRST argument (:1186-1187)."""
+    v, w = sol["v"], sol["w"]
+    zeta = _cscale(v, 1.0 / cnorm(v))
+    return zeta, _cscale(w, 1.0 / cinner(zeta, w))
+
+
+def _hopf_record(prob, X: HopfVec, zeta, zeta_star, a, b, P001, P110, P200, cv, it, bad=None) -> Hopf:
+    p, om = float(X.p[0]), float(X.p[1])
+    return Hopf(x0=X.u, p=p, omega=om, zeta=zeta, zeta_star=zeta_star, nf=HopfNormalForm(a, b, P110, P001, P200),
+                type=hopf_type(b), params=prob._pvec(p), lens=prob.lens, converged=bool(cv), itlinear=tuple(int(i) for i in it),
+                unconverged_solves=bad)
+
+
+def hopf_normal_form(prob, X: HopfVec, zeta, zeta_star, ls: _GMRES) -> Hopf:
+    """__hopf_normal_form (:1009-1076) call by call on the plugin surface at the Hopf point X = (x, [p, omega]) with
+    zeta, zeta* normalised (hopf_eigenpair): Psi001 = ls(J, -dpF) and Psi110 = ls(J, -d2F[zeta, conj zeta]) as one
+    ls(J, rhs1, rhs2) (bk_gmres2), Psi200 = ls.solve_complex(J, d2F[zeta, zeta] / 2, a0 = 2 i omega, a1 = -1) (:1053), the
+    right-hand sides from hopf_nf_rhs and (a, b) from hopf_nf_contract."""
+    x, p, om = X.u, float(X.p[0]), float(X.p[1])
+    pv, ipar = prob._pvec(p), prob.ipar
+    nrm = hopf_contract(prob, x, pv, ipar, zeta, zeta_star)[2].conjugate()         # <zeta, zeta*> = conj(zeta*^H zeta)
+    if not abs(nrm - 1) <= 1e-8:
+        raise ValueError(f"Error of precision in normalization: <zeta, zeta*> = {nrm}, expected 1")
+    J = prob.jacobian(x, p)
+    r20, r11 = hopf_nf_rhs(prob, x, pv, zeta)
+    P001, P110, cv, it = _solve2(ls, J, dpF(prob, x, pv, ipar).scale_(-1.0), r11.scale_(-1.0))
+    P200, cv2, it2 = ls.solve_complex(J, r20, a0=complex(0.0, 2.0 * om), a1=-1.0)
+    a, b = hopf_nf_contract(prob, x, pv, ipar, zeta, zeta_star, P001, P110, P200)
+    return _hopf_record(prob, X, zeta, zeta_star, a, b, P001, P110, P200, cv and cv2, (it[0], it[1], it2))
+
+
+def hopf_normal_form_native(prob, X: HopfVec, zeta, zeta_star, ls: _GMRES) -> Hopf:
+    """The same as one library call (bk_hopf_normal_form)."""
+    ctx = prob.ctx
+    x, p, om = X.u, float(X.p[0]), float(X.p[1])
+    pv = prob._pvec(p)
+    P001, P110, P200 = x.similar(), x.similar(), (x.similar(), x.similar())
+    ab = (C.c_double * 4)()
+    cv = C.c_int()
+    it = (C.c_int * 3)()
+    lo = ls._opts()
+    bad0 = ctx.get_option("hopf_nf_unconverged_solves")
+    ctx.check(ctx.lib.bk_hopf_normal_form(ctx.h, prob.h, _ptr(x.t), _carr(pv), len(pv), prob.ipar, om, _ptr(zeta[0].t),
+                                          _ptr(zeta[1].t), _ptr(zeta_star[0].t), _ptr(zeta_star[1].t), C.byref(lo), ls._pl(),
+                                          _ptr(P001.t), _ptr(P110.t), _ptr(P200[0].t), _ptr(P200[1].t), ab, C.byref(cv), it),
+              "bk_hopf_normal_form")
+    return _hopf_record(prob, X, zeta, zeta_star, complex(ab[0], ab[1]), complex(ab[2], ab[3]), P001, P110, P200, cv.value,
+                        (it[0], it[1], it[2]), int(ctx.get_option("hopf_nf_unconverged_solves") - bad0))
+
+
+def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, max_iterations=15, norm_inf=False, seed=0) -> Hopf:
+    """get_normal_form(br, ind) (src/NormalForms.jl:1102-1204) for a point of type "hopf" of a branch of
+    continuation.continuation_native(..., bisection = True, save_sol = True): hopf_point -> hopf_start_vectors (the reference's
+    random start, or start_with_eigen when ``eig`` is given) -> newton_hopf_native -> hopf_eigenpair -> hopf_normal_form_native.
+    The normal form is taken at the REFINED point (the reference takes the bisected one)."""
+    kind = br.specialpoint[ind].get("type")
+    if kind != "hopf":
+        raise NotImplementedError(f"get_normal_form: point {ind} is of type {kind!r}; only the Hopf normal form (hopf_normal_form) is "
+                                  "available -- fold and branch points have refinement (newton_fold) and fold-curve continuation "
+                                  "(continuation_fold), no normal form")
+    X = hopf_point(br, ind)
+    a, b = hopf_start_vectors(prob, X, ls, eig=eig, nev=nev, seed=seed)
+    s = newton_hopf_native(prob, X, a, b, ls, tol=tol, max_iterations=max_iterations, norm_inf=norm_inf)
+    if not s["converged"]:
+        raise RuntimeError(f"get_normal_form: newton_hopf did not converge from the bisected point (residuals {s['residuals']})")
+    zeta, zeta_star = hopf_eigenpair(prob, s)
+    return hopf_normal_form_native(prob, s["u"], zeta, zeta_star, ls)
+
+
+class HopfOrbit:
+    """t -> x0 + 2 Re(zeta A(t)) + ds Psi001 + |A(t)|^2 Psi110 + 2 Re(A(t)^2 Psi200), A(t) = amp e^{i t} (:1262-1271), 2 pi
+    periodic.  ``orbit(t)`` is one HipVec; ``orbit.slices(M)`` the M equidistant phases t_m = 2 pi m / M, eight per pass over the
+    inputs -- the initial guess of a time-discretised periodic orbit."""
+
+    def __init__(self, hopf: Hopf, ds, amp, Psi001, Psi110, Psi200):
+        self.hopf, self.ds, self.amp = hopf, float(ds), float(amp)
+        self.Psi = (Psi001, Psi110, Psi200)
+
+    def _psi(self):
+        P001, P110, P200 = self.Psi
+        if P001 is None:                            # no coefficients: the guess from the eigenvector alone (:1253-1260)
+            z = self.hopf.x0.zerovector()
+            P001, P110, P200 = z, z, (z, z)
+        return P001, P110, P200
+
+    def at(self, ts):
+        h = self.hopf
+        return hopf_orbit(h.x0, h.zeta, *self._psi(), self.ds, self.amp, ts)
+
+    def __call__(self, t: float) -> HipVec:
+        return self.at([t])[0]
+
+    def slices(self, M: int):
+        return self.at([2.0 * math.pi * m / M for m in range(int(M))])
+
+
+def predictor(hopf: Hopf, ds: float, ampfactor=1.0) -> dict:
+    """predictor(hp::Hopf, ds; ampfactor) (:1227-1281): dict(orbit, Psi001, amp, omega, period, p, dsfactor).  With the
+    coefficients a, b the side of the Hopf point where the orbits live is dsfactor = +1 when Re a Re b < 0, else -1,
+    p = hopf.p + |ds| dsfactor, the amplitude solves Re a dp + Re b amp^2 = 0 and omega is corrected to
+    omega + (Im a - Im b Re a / Re b) ds; the returned ``amp`` is twice the one the orbit uses, as in the reference (:1276)."""
+    nf = hopf.nf
+    if nf is not None and nf.a is not None and nf.b is not None:
+        a, b = complex(nf.a), complex(nf.b)
+        if b.real == 0.0:
+            raise ValueError(f"The Lyapunov coefficient is zero (b = {b}): the Hopf point is singular, no predictor")
+        dsfactor = 1 if a.real * b.real < 0 else -1
+        dsnew = abs(ds) * dsfactor
+        pnew = hopf.p + dsnew
+        amp = ampfactor * math.sqrt(-dsnew * a.real / b.real)
+        omega = hopf.omega + (a.imag - b.imag * a.real / b.real) * ds
+        P001, P110, P200 = nf.Psi001, nf.Psi110, nf.Psi200
+    else:
+        amp, omega, pnew, dsfactor = ampfactor, hopf.omega, hopf.p + ds, 1
+        P001 = P110 = P200 = None
+    return dict(orbit=HopfOrbit(hopf, ds, amp, P001, P110, P200), Psi001=P001, amp=2 * amp, omega=omega,
+                period=abs(2 * math.pi / omega), p=pnew, dsfactor=dsfactor)

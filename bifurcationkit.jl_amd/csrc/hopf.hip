@@ -8,11 +8,12 @@
 //   NL(z) = (r + i nu) z - (c3 + i mu) |z|^2 z - c5 |z|^4 z + gamma,   z = u1 + i u2,
 // is pointwise and the Laplacian is linear, so d2F = d2NL: per grid point one symmetric 2 x 2 matrix H_f(u) for each field f,
 // d2F_f[a, b] = a^T H_f b.  H_f are the u-derivatives of the closed-form Jacobian of stencil.hip:cgl_kernel (f1u, f1v, f2u, f2v);
-// dJ/dp is the u-derivative of dparam_kernel's phi_p, a 2 x 2 matrix D_p(u) per point (zero for gamma).  Complex vectors are
-// (re, im) pairs of real device vectors; d2F and dJ/dp act on them by linearity.
+// dJ/dp is the u-derivative of dparam_kernel's phi_p, a 2 x 2 matrix D_p(u) per point (zero for gamma); both in hopf_pw.h.
+// Complex vectors are (re, im) pairs of real device vectors; d2F and dJ/dp act on them by linearity.
 #include <cmath>
 
 #include "common.h"
+#include "hopf_pw.h"
 #include "minaug.h"
 #include "ops.h"
 #include "stream.h"
@@ -20,36 +21,6 @@
 namespace bk {
 
 namespace {
-
-// ------------------------------------------------------------------ pointwise tensors
-struct CglCoef { double mu, c3, c5; int ipar; };
-
-// Hessian of NL at (u1, u2): H1 = [[h[0], h[1]], [h[1], h[2]]] (field 1), H2 = [[h[3], h[4]], [h[4], h[5]]] (field 2)
-__device__ __forceinline__ void cgl_hess(const CglCoef& c, double u1, double u2, double h[6]) {
-    const double ua = u1 * u1 + u2 * u2;
-    const double q1 = u1 * (8.0 * u1 * u1 + 12.0 * ua), q2 = u2 * (8.0 * u1 * u1 + 4.0 * ua);
-    const double q3 = u1 * (8.0 * u2 * u2 + 4.0 * ua), q4 = u2 * (8.0 * u2 * u2 + 12.0 * ua);
-    h[0] = -6.0 * c.c3 * u1 + 2.0 * c.mu * u2 - c.c5 * q1;
-    h[1] = -2.0 * c.c3 * u2 + 2.0 * c.mu * u1 - c.c5 * q2;
-    h[2] = -2.0 * c.c3 * u1 + 6.0 * c.mu * u2 - c.c5 * q3;
-    h[3] = -2.0 * c.c3 * u2 - 6.0 * c.mu * u1 - c.c5 * q2;
-    h[4] = -2.0 * c.c3 * u1 - 2.0 * c.mu * u2 - c.c5 * q3;
-    h[5] = -6.0 * c.c3 * u2 - 2.0 * c.mu * u1 - c.c5 * q4;
-}
-
-// dJ/dp at (u1, u2) for params[ipar] = (r, mu, nu, c3, c5, gamma): D = [[d[0], d[1]], [d[2], d[3]]]
-__device__ __forceinline__ void cgl_djdp(int ipar, double u1, double u2, double d[4]) {
-    const double ua = u1 * u1 + u2 * u2;
-    switch (ipar) {
-        case 0: d[0] = 1.0; d[1] = 0.0; d[2] = 0.0; d[3] = 1.0; break;
-        case 1: d[0] = 2.0 * u1 * u2; d[1] = 2.0 * u2 * u2 + ua; d[2] = -(2.0 * u1 * u1 + ua); d[3] = -2.0 * u1 * u2; break;
-        case 2: d[0] = 0.0; d[1] = -1.0; d[2] = 1.0; d[3] = 0.0; break;
-        case 3: d[0] = -(2.0 * u1 * u1 + ua); d[1] = -2.0 * u1 * u2; d[2] = d[1]; d[3] = -(2.0 * u2 * u2 + ua); break;
-        case 4: d[0] = -(4.0 * ua * u1 * u1 + ua * ua); d[1] = -4.0 * ua * u1 * u2; d[2] = d[1];
-                d[3] = -(4.0 * ua * u2 * u2 + ua * ua); break;
-        default: d[0] = d[1] = d[2] = d[3] = 0.0; break;
-    }
-}
 
 // ------------------------------------------------------------------ kernels
 // out = d2F(u)[x1, x2] (x2 != NULL) or dJ/dp(u) x1 (x2 == NULL) on the two stacked fields of N points each (bk_hopf_d2f,
@@ -187,17 +158,6 @@ static int v_hopf_contract(bk_ctx* ctx, size_t n, const double* u, const double*
 }
 
 // ------------------------------------------------------------------ the formulation
-int hopf_coef(bk_problem* prob, const double* params, int nparams, int ipar, CglCoef* c) {
-    bk_ctx* ctx = prob->ctx;
-    if (prob->desc.pde != BK_PDE_CGL2D)
-        return set_error(ctx, "hopf: the minimally augmented Hopf formulation is available for BK_PDE_CGL2D only "
-                              "(analytic Hessian of the cGL nonlinearity), not for problem kind %d", prob->desc.pde);
-    if (nparams != 6) return set_error(ctx, "hopf: BK_PDE_CGL2D takes params = {r, mu, nu, c3, c5, gamma} (got %d)", nparams);
-    if (ipar < 0 || ipar > 5) return set_error(ctx, "hopf: bad parameter index %d", ipar);
-    c->mu = params[1]; c->c3 = params[3]; c->c5 = params[4]; c->ipar = ipar;
-    return 0;
-}
-
 // normN of BorderedArray(F, [Re sigma, Im sigma]); the max norm propagates a NaN from any component (as v_nrminf does)
 int norm_hopf(bk_ctx* ctx, size_t n, const double* f, const double sigma[2], bool inf, double* out) {
     double r;

@@ -556,6 +556,46 @@ int bk_newton_hopf(bk_ctx* ctx, bk_problem* prob, double* x, double* p, double* 
                    const bk_newton_opts* nopts, const bk_gmres_opts* lsopts, bk_precond* pl, double* v_re, double* v_im,
                    double* w_re, double* w_im, double sigma[2], bk_newton_result* res);
 
+/* ------------------------------------------------------------------ Hopf normal form ---------------------
+ * __hopf_normal_form (src/NormalForms.jl:1009-1076) and the orbit of predictor(::Hopf, ds) (:1227-1281), matrix-free, for
+ * BK_PDE_CGL2D (any other problem: the error of the Hopf entries above).  At a Hopf point (x, params, omega) with zeta the
+ * eigenvector of J for i omega and zeta* that of J' for -i omega -- the v and w bk_newton_hopf returns, scaled to |zeta| = 1 and
+ * <zeta, zeta*> = 1 with inner(x, y) = sum conj(x) y -- the coefficients of z' = z (i omega + a dp + b |z|^2) are
+ *   a = < dJ/dp zeta + d2F[zeta, Psi001], zeta* >,
+ *   b = < d2F[zeta, Psi110] + d2F[conj zeta, Psi200] + d3F[zeta, zeta, conj zeta] / 2, zeta* >,
+ *   Psi001 = -J \ dpF,  Psi110 = -J \ d2F[zeta, conj zeta],  Psi200 = (2 i omega - J) \ (d2F[zeta, zeta] / 2).
+ * dpF and dJ/dp are analytic where the reference differentiates (:1032-1047).  Complex vectors are (re, im) pairs.          */
+/* out = d3F(u, params)[dx1, dx2, dx3] for real arguments (the d3F of R3, :1029): per grid point and field the symmetric
+ * 2 x 2 x 2 third derivative of the cGL nonlinearity (examples/cGL2d.jl:24-40); complex arguments by linearity.           */
+int bk_hopf_d3f(bk_problem* prob, const double* u, const double* params, int nparams, const double* dx1, const double* dx2,
+                const double* dx3, double* out);
+/* One pass over u and zeta: (r20_re, r20_im) = d2F[zeta, zeta] / 2 = R2(zeta, zeta) (:1052) and r11 = d2F[zeta, conj zeta]
+ * = 2 R2(zeta, conj zeta) (:1057; real).  The outputs are distinct and alias no input.                                     */
+int bk_hopf_nf_rhs(bk_problem* prob, const double* u, const double* params, int nparams, const double* z_re, const double* z_im,
+                   double* r20_re, double* r20_im, double* r11);
+/* One streaming pass over u, zeta, zeta*, Psi001, Psi110 and Psi200: host out[4] = (Re a, Im a, Re b, Im b), the two inner
+ * products of :1049 and :1063 for params[ipar].  Deterministic, all-reduced.                                              */
+int bk_hopf_nf_contract(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* z_re,
+                        const double* z_im, const double* zs_re, const double* zs_im, const double* psi001, const double* psi110,
+                        const double* psi200_re, const double* psi200_im, double out[4]);
+/* The whole of __hopf_normal_form (:1009-1076) at (x, params, omega) for params[ipar]: analytic dpF, the pass of
+ * bk_hopf_nf_rhs, the two real solves as one two-lane pair (as bk_gmres2), the shifted solve (bk_gmres_cshift with
+ * a0 = 2 i omega, a1 = -1, :1053) and the pass of bk_hopf_nf_contract.  zeta and zeta* come normalised; unless
+ * |<zeta, zeta*> - 1| <= 1e-8 the call is an error (:1186-1189).  ab[4] = (Re a, Im a, Re b, Im b); the four Psi vectors are
+ * outputs, distinct from each other and from the inputs.  *converged = all three solves converged; itlinear[3] = GMRES counts
+ * of the Psi001, Psi110 and Psi200 solves.  An unconverged solve is no error (the reference logs it, :1039): each adds 1 to the
+ * context counter "hopf_nf_unconverged_solves".                                                                            */
+int bk_hopf_normal_form(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar, double omega,
+                        const double* z_re, const double* z_im, const double* zs_re, const double* zs_im,
+                        const bk_gmres_opts* lsopts, bk_precond* pl, double* psi001, double* psi110, double* psi200_re,
+                        double* psi200_im, double ab[4], int* converged, int itlinear[3]);
+/* The orbit of predictor(::Hopf, ds) (:1262-1271) at the M phases t[0..M) (host): device vectors of length n
+ *   out[m] = x0 + 2 Re(zeta A_m) + ds Psi001 + |A_m|^2 Psi110 + 2 Re(A_m^2 Psi200),   A_m = amp e^{i t[m]},
+ * up to eight phases per pass over the seven inputs.  The outputs are distinct and alias no input.                         */
+int bk_hopf_orbit(bk_ctx* ctx, size_t n, const double* x0, const double* z_re, const double* z_im, const double* psi001,
+                  const double* psi110, const double* psi200_re, const double* psi200_im, double ds, double amp, int M,
+                  const double* t, double* const* out);
+
 #ifdef __cplusplus
 }
 #endif
