@@ -202,6 +202,13 @@ SIGNATURES = {
     "bk_hopf_normal_form": (I, [VP, VP, VP, c_double_p, I, I, D, VP, VP, VP, VP, C.POINTER(GmresOpts), VP, VP, VP, VP, VP,
                                 c_double_p, c_int_p, c_int_p]),
     "bk_hopf_orbit": (I, [VP, SZ, VP, VP, VP, VP, VP, VP, VP, D, D, I, c_double_p, C.POINTER(VP)]),
+    "bk_d3f": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP]),
+    "bk_nf1d_dots": (I, [VP, VP, c_double_p, I, I, VP, VP, c_double_p]),
+    "bk_nf1d_rhs": (I, [VP, VP, c_double_p, I, I, VP, D, D, VP, VP]),
+    "bk_nf1d_contract": (I, [VP, VP, c_double_p, I, I, VP, VP, VP, VP, c_double_p]),
+    "bk_nf1d_predict": (I, [VP, SZ, VP, VP, VP, VP, I, c_double_p, c_double_p, c_double_p, C.POINTER(VP)]),
+    "bk_normal_form_1d": (I, [VP, VP, VP, c_double_p, I, I, VP, VP, C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP, VP, VP,
+                              c_double_p, c_int_p, c_int_p]),
 }
 
 _lib = None

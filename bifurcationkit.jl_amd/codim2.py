@@ -826,7 +826,8 @@ def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls
 #   hopf_eigenpair            zeta, zeta* from the null vectors v, w of a newton_hopf result, |zeta| = 1, <zeta, zeta*> = 1
 #   hopf_normal_form          the computation call by call on the plugin surface (ls(J, rhs1, rhs2), ls.solve_complex)
 #   hopf_normal_form_native   the same as one library call (bk_hopf_normal_form)
-#   get_normal_form           get_normal_form(br, ind) for a Hopf point of a native branch: refine, then the normal form
+#   get_normal_form           get_normal_form(br, ind) for a Hopf point of a native branch: refine, then the normal form ("bp" and
+#                             "fold" points of the Swift-Hohenberg problems: normal_form1d.py)
 #   predictor                 the second-order guess of the periodic orbit that branches off
 #
 # z' = z (i omega + a dp + b |z|^2); inner(x, y) = sum conj(x) y = cinner(x, y), so a = cinner(av, zeta*), b = cinner(bv, zeta*).
@@ -954,12 +955,20 @@ def hopf_normal_form_native(prob, X: HopfVec, zeta, zeta_star, ls: _GMRES) -> Ho
                         (it[0], it[1], it[2]), int(ctx.get_option("hopf_nf_unconverged_solves") - bad0))
 
 
-def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, max_iterations=15, norm_inf=False, seed=0) -> Hopf:
+def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, max_iterations=15, norm_inf=False, seed=0,
+                    bls=None, refine=True):
     """get_normal_form(br, ind) (src/NormalForms.jl:1102-1204) for a point of type "hopf" of a branch of
     continuation.continuation_native(..., bisection = True, save_sol = True): hopf_point -> hopf_start_vectors (the reference's
     random start, or start_with_eigen when ``eig`` is given) -> newton_hopf_native -> hopf_eigenpair -> hopf_normal_form_native.
-    The normal form is taken at the REFINED point (the reference takes the bisected one)."""
+    The normal form is taken at the REFINED point (the reference takes the bisected one).  For a Swift-Hohenberg problem a point of
+    type "bp" or "fold" goes to normal_form1d.get_normal_form1d (``bls``, ``refine`` as there) and returns its SimpleBranchPoint;
+    "nd" points, and "bp" / "fold" points of any other problem, have no normal form here."""
+    from . import normal_form1d as N1
+    sh = N1.is_sh_problem(prob)                     # decided before the branch is looked at
     kind = br.specialpoint[ind].get("type")
+    if sh and kind in ("bp", "fold"):
+        return N1.get_normal_form1d(br, ind, prob, ls, bls=bls, eig=eig, nev=nev, refine=refine, tol=tol,
+                                    max_iterations=max_iterations, norm_inf=norm_inf)
     if kind != "hopf":
         raise NotImplementedError(f"get_normal_form: point {ind} is of type {kind!r}; only the Hopf normal form (hopf_normal_form) is "
                                   "available -- fold and branch points have refinement (newton_fold) and fold-curve continuation "
@@ -1000,11 +1009,15 @@ class HopfOrbit:
         return self.at([2.0 * math.pi * m / M for m in range(int(M))])
 
 
-def predictor(hopf: Hopf, ds: float, ampfactor=1.0) -> dict:
-    """predictor(hp::Hopf, ds; ampfactor) (:1227-1281): dict(orbit, Psi001, amp, omega, period, p, dsfactor).  With the
+def predictor(hopf, ds: float, ampfactor=1.0):
+    """predictor(bp, ds; ampfactor).  A SimpleBranchPoint record goes to normal_form1d.predictor (:389-531).  For a Hopf record,
+    predictor(hp::Hopf, ds; ampfactor) (:1227-1281): dict(orbit, Psi001, amp, omega, period, p, dsfactor).  With the
     coefficients a, b the side of the Hopf point where the orbits live is dsfactor = +1 when Re a Re b < 0, else -1,
     p = hopf.p + |ds| dsfactor, the amplitude solves Re a dp + Re b amp^2 = 0 and omega is corrected to
     omega + (Im a - Im b Re a / Re b) ds; the returned ``amp`` is twice the one the orbit uses, as in the reference (:1276)."""
+    if not isinstance(hopf, Hopf):
+        from . import normal_form1d as N1
+        return N1.predictor(hopf, ds, ampfactor=ampfactor)
     nf = hopf.nf
     if nf is not None and nf.a is not None and nf.b is not None:
         a, b = complex(nf.a), complex(nf.b)

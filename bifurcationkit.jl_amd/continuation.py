@@ -477,19 +477,14 @@ def continuation_native(prob, x0, p0, alg: PALC, cp: ContinuationPar, normC=norm
     ``finalise_solution(state, r) -> bool`` (the reference's hook of the same name, src/Continuation.jl:296-310) is called
     after every accepted step with a ``get()`` accessor of the device state; returning False stops the run.
     ``cp.save_sol_every_step`` / ``cp.save_to_file`` / ``filename`` as in :func:`continuation`."""
-    import ctypes as C
-
-    from . import _lib as L
     from . import hip
 
     alg = alg.update(cp)
     nopt = cp.newton_options
-    ls, bls = nopt.linsolver, alg.bls
+    ls = nopt.linsolver
     if normC not in (norm2, norminf):
         raise TypeError("continuation_native: normC must be norm2 or norminf")
     inf = normC is norminf
-    ctx = prob.ctx
-    eig = nopt.eigsolver if cp.detect_bifurcation > 0 else None
     s0 = hip.newton_native(prob, x0, p0, ls, nopt.tol, nopt.max_iterations, inf, callback=callback_newton)
     if not s0["converged"]:
         raise RuntimeError("Newton failed to converge for the initial guess on the branch")
@@ -497,6 +492,25 @@ def continuation_native(prob, x0, p0, alg: PALC, cp: ContinuationPar, normC=norm
     s1 = hip.newton_native(prob, s0["u"], p1, ls, nopt.tol, nopt.max_iterations, inf, callback=callback_newton)
     if not s1["converged"]:
         raise RuntimeError("Newton failed to converge. Required for the computation of the initial tangent")
+    return _continuation_native_from(prob, s0, p0, s1, p1, alg, cp, inf, verbosity, save_sol, bisection, finalise_solution,
+                                     callback_newton, on_init, filename)
+
+
+def _continuation_native_from(prob, s0, p0, s1, p1, alg: PALC, cp: ContinuationPar, inf, verbosity, save_sol, bisection,
+                              finalise_solution, callback_newton, on_init, filename) -> ContResult:
+    """The body of :func:`continuation_native` after its two initial Newton solves: the branch from the two points
+    (s0["u"], p0), (s1["u"], p1) -- ``bk_cont_create`` builds the secant tangent from them -- with ``alg`` already updated.
+    ``s0`` carries the record of the first point (u, itnewton, itlineartot, residuals).  Also the entry of the two-point start of
+    branch switching (continuation(prob, x0, par0, x1, p1, ...), src/bifdiagram/BranchSwitching.jl:8-44)."""
+    import ctypes as C
+
+    from . import _lib as L
+    from . import hip
+
+    nopt = cp.newton_options
+    bls = alg.bls
+    ctx = prob.ctx
+    eig = nopt.eigsolver if cp.detect_bifurcation > 0 else None
     big = 1.7e308
     co = L.ContOpts(cp.ds, cp.dsmin, cp.dsmax, cp.a, alg.theta, max(cp.p_min, -big), min(cp.p_max, big),
                     0 if alg.tangent == "secant" else 1, 1 if eig is not None else 0, cp.nev, cp.tol_stability)

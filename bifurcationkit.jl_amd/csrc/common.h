@@ -102,6 +102,7 @@ struct bk_ctx {
         double fold_unconverged = 0.0;                                             // bk_newton_fold: bordered-vector / step solves that returned unconverged
         double hopf_unconverged = 0.0;                                             // bk_newton_hopf: the same count for the Hopf system
         double hopf_nf_unconverged = 0.0;                                          // bk_hopf_normal_form: solves (of three per call) that returned unconverged
+        double nf1d_unconverged = 0.0;                                             // bk_normal_form_1d: solves (three with bordering, two matrix-free) that returned unconverged
     } diag;
     double* diag_slot(const std::string& key) {
         if (key == "gmres_block_steps") return &diag.block_steps;
@@ -113,6 +114,7 @@ struct bk_ctx {
         if (key == "fold_unconverged_solves") return &diag.fold_unconverged;
         if (key == "hopf_unconverged_solves") return &diag.hopf_unconverged;
         if (key == "hopf_nf_unconverged_solves") return &diag.hopf_nf_unconverged;
+        if (key == "nf1d_unconverged_solves") return &diag.nf1d_unconverged;
         return nullptr;
     }
     std::vector<double> newton_shifts; // option gmres_newton_carry: Leja-ordered Ritz values of the last GMRES solve (solver.hip)

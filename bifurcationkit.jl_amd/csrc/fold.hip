@@ -4,8 +4,8 @@
 //
 // The Swift-Hohenberg problems are symmetric (J' = J, :79-84), so the adjoint system is the same bordered solve with a and b
 // exchanged, and no solve at all when a and b are the same vector.  Their second derivative d2F(x, p)[dx1, dx2] =
-// h(u) dx1 dx2 and the parameter derivative of J, dJ/dp = diag(g_p(u)), are pointwise polynomials (vecops.hip: fold_pw_kernel,
-// fold_contract_kernel):
+// h(u) dx1 dx2 and the parameter derivative of J, dJ/dp = diag(g_p(u)), are pointwise polynomials (fold_pw.h; fold_pw_kernel,
+// fold_contract_kernel below):
 //   BK_PDE_SH   h = 2 nu - 6 u                (examples/SH2d-fronts.jl:40)   g_l = 1,  g_nu = 2 u
 //   BK_PDE_SH1D h = 6 nu u - 20 u^3           (examples/SHpde_snaking.jl:26) g_lam = 1, g_nu = 3 u^2
 // so sigma_p = -<w, dJ/dp v> (:90-95), dpF (:88-89) and sigma_x . X (:153-157) are evaluated analytically: the reference's
@@ -13,6 +13,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "fold_pw.h"
 #include "minaug.h"
 #include "ops.h"
 #include "stream.h"
@@ -22,11 +23,6 @@ namespace bk {
 namespace {
 
 // ------------------------------------------------------------------ kernels
-// Pointwise polynomial factors c[0] + u (c[1] + u (c[2] + u c[3])) of d2F (h) and dJ/dp (g), evaluated in this one fixed
-// Horner order (tests/test_gpu_fold.py restates it).
-struct FoldPoly { double h[4]; double g[4]; };
-__device__ __forceinline__ double fold_poly(const double* c, double u) { return c[0] + u * (c[1] + u * (c[2] + u * c[3])); }
-
 // out = (f(u) x1) x2, or f(u) x1 when x2 is NULL: d2F(u)[x1, x2] and dJ/dp(u) x1 (bk_d2f, bk_djdp)
 __global__ void __launch_bounds__(kThreads) fold_pw_kernel(size_t n, const double* __restrict__ u, FoldPoly P,
                                                            const double* __restrict__ x1, const double* __restrict__ x2,
@@ -132,27 +128,6 @@ static int v_fold_contract(bk_ctx* ctx, size_t n, const double* u, const double*
 }
 
 // ------------------------------------------------------------------ the formulation
-// polynomial coefficients (c0 + u (c1 + u (c2 + u c3))) of h(u) and g_ipar(u); an error for problems without the formulation
-int fold_polys(bk_problem* prob, const double* params, int nparams, int ipar, double h[4], double g[4]) {
-    bk_ctx* ctx = prob->ctx;
-    const int pde = prob->desc.pde;
-    if (pde != BK_PDE_SH && pde != BK_PDE_SH1D)
-        return set_error(ctx, "fold: the minimally augmented fold formulation is available for BK_PDE_SH and BK_PDE_SH1D only "
-                              "(symmetric Jacobian with an analytic Hessian), not for problem kind %d", pde);
-    if (nparams < 2 || nparams > BK_MAX_PARAMS) return set_error(ctx, "fold: the SH problems take params = {l | lambda, nu}");
-    if (ipar < 0 || ipar > 1) return set_error(ctx, "fold: bad parameter index %d", ipar);
-    const double nu = params[1];
-    for (int i = 0; i < 4; ++i) h[i] = g[i] = 0.0;
-    if (pde == BK_PDE_SH) {
-        h[0] = 2.0 * nu; h[1] = -6.0;
-        if (ipar == 0) g[0] = 1.0; else g[1] = 2.0;
-    } else {
-        h[1] = 6.0 * nu; h[3] = -20.0;
-        if (ipar == 0) g[0] = 1.0; else g[2] = 3.0;
-    }
-    return 0;
-}
-
 int norm_fold(bk_ctx* ctx, size_t n, const double* f, double sigma, bool inf, double* out) {
     double r;
     if (inf) {

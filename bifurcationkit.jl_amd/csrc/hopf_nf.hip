@@ -198,14 +198,6 @@ __global__ void __launch_bounds__(kThreads) hopf_orbit_kernel(size_t n, const do
 }
 
 // ------------------------------------------------------------------ launchers
-// launch(VEC, NTH) as integral constants: non-temporal 16-byte loads (nth), 16-byte loads (vec) or element by element
-template <class Launch>
-void load_path_dispatch(bool vec, bool nth, Launch&& launch) {
-    if (nth) launch(std::integral_constant<int, 2>{}, std::true_type{});
-    else if (vec) launch(std::integral_constant<int, 2>{}, std::false_type{});
-    else launch(std::integral_constant<int, 1>{}, std::false_type{});
-}
-
 int v_hopf_d3(bk_ctx* ctx, size_t n, const double* u, const CglCoef& c, const double* x1, const double* x2, const double* x3,
               double* out) {
     const size_t N = n / 2;

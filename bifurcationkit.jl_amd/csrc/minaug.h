@@ -33,15 +33,20 @@ __device__ __forceinline__ void block_sum_store(const double (&s)[NV], double* p
     }
 }
 
-// launch(M, VEC, NTH) as integral constants for a kernel template <int M, int VEC, bool NTH>: m = 0..3 extra vectors, streamed
-// with non-temporal 16-byte loads (nth), 16-byte loads (vec) or element by element
+// launch(VEC, NTH) as integral constants: the load path of a streaming kernel template <..., int VEC, bool NTH> -- non-temporal
+// 16-byte loads (nth), 16-byte loads (vec) or element by element (fold.hip, hopf.hip, hopf_nf.hip, nf1d.hip)
+template <class Launch>
+void load_path_dispatch(bool vec, bool nth, Launch&& launch) {
+    if (nth) launch(std::integral_constant<int, 2>{}, std::true_type{});
+    else if (vec) launch(std::integral_constant<int, 2>{}, std::false_type{});
+    else launch(std::integral_constant<int, 1>{}, std::false_type{});
+}
+
+// launch(M, VEC, NTH) as integral constants for a kernel template <int M, int VEC, bool NTH>: m = 0..3 extra vectors, each on
+// the load path of load_path_dispatch
 template <class Launch>
 void contract_dispatch(int m, bool vec, bool nth, Launch&& launch) {
-    auto variant = [&](auto M) {
-        if (nth) launch(M, std::integral_constant<int, 2>{}, std::true_type{});
-        else if (vec) launch(M, std::integral_constant<int, 2>{}, std::false_type{});
-        else launch(M, std::integral_constant<int, 1>{}, std::false_type{});
-    };
+    auto variant = [&](auto M) { load_path_dispatch(vec, nth, [&](auto V, auto NT) { launch(M, V, NT); }); };
     switch (m) {
         case 0: variant(std::integral_constant<int, 0>{}); break;
         case 1: variant(std::integral_constant<int, 1>{}); break;

@@ -596,6 +596,52 @@ int bk_hopf_orbit(bk_ctx* ctx, size_t n, const double* x0, const double* z_re, c
                   const double* psi110, const double* psi200_re, const double* psi200_im, double ds, double amp, int M,
                   const double* t, double* const* out);
 
+/* ------------------------------------------------------------------ normal form, 1-D kernel -------------
+ * get_normal_form1d (src/NormalForms.jl:189-353) and the vectors of its predictors (:389-531), matrix-free, for BK_PDE_SH
+ * (2-D / 3-D) and BK_PDE_SH1D (any other problem: the error of the fold entries above).  At a simple branch point or fold
+ * (x, params) with the kernel vector zeta of J and zeta* of J' = J, |zeta| = 1 and <zeta, zeta*> = 1 (zeta* = zeta /
+ * <zeta, zeta> in the is_symmetric branch, :261-263; the two pointers may be equal), E(r) = r - <r, zeta*> zeta:
+ *   a01 = <dpF, zeta*>,  b11 = <dJ/dp zeta + d2F[zeta, Psi01], zeta*>,  a02 = <2 dJ/dp Psi01 + d2F[Psi01, Psi01], zeta*>,
+ *   b20 = <d2F[zeta, zeta], zeta*>,  b30 = <d3F[zeta, zeta, zeta] + 3 d2F[zeta, Psi20], zeta*>,
+ *   [J zeta*; zeta' 0][Psi01; s] = [E(-dpF); 0],   [J zeta*; zeta' 0][Psi20; s] = [E(-d2F[zeta, zeta]); 0]   (:299-336)
+ * in a01 dp + a02 dp^2 / 2 + b11 x dp + b20 x^2 / 2 + b30 x^3 / 6.  dpF, dJ/dp, d2F and d3F are pointwise and analytic and
+ * d2F/dp2 = 0, where the reference uses ForwardDiff or central differences (:289-321).                                    */
+/* out = d3F(u, params)[dx1, dx2, dx3] (the R3 of :283): SH -6 dx1 dx2 dx3, SH1D (6 nu - 60 u^2) dx1 dx2 dx3; pointwise.   */
+int bk_d3f(bk_problem* prob, const double* u, const double* params, int nparams, const double* dx1, const double* dx2,
+           const double* dx3, double* out);
+/* One streaming pass over u, zeta, zeta* that writes nothing: host out[3] = (a01, b20, <zeta, zeta*>) for params[ipar]
+ * (:299, :329, :275).  Deterministic, all-reduced.                                                                         */
+int bk_nf1d_dots(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* zeta,
+                 const double* zeta_star, double out[3]);
+/* One pass over u and zeta: the projected right-hand sides r01 = E(-dpF) = a01 zeta - dpF and r20 = E(-d2F[zeta, zeta]) =
+ * b20 zeta - d2F[zeta, zeta] of the two bordered solves (:303, :333) with the a01, b20 of bk_nf1d_dots.  The outputs are
+ * distinct and alias no input.                                                                                              */
+int bk_nf1d_rhs(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* zeta, double a01,
+                double b20, double* r01, double* r20);
+/* One streaming pass over u, zeta, zeta*, Psi01, Psi20: host out[3] = (b11, a02, b30) for params[ipar] (:313, :323, :336).
+ * Deterministic, all-reduced.                                                                                                */
+int bk_nf1d_contract(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* zeta,
+                     const double* zeta_star, const double* psi01, const double* psi20, double out[3]);
+/* The vectors of the predictors (:410-419 Transcritical, :480 Pitchfork, :524 BranchPoint): M <= 4 device vectors of length n
+ *   out[k] = ((x0 + alpha[k] zeta) + beta[k] Psi01) + gamma[k] tau
+ * in one pass over the inputs (host coefficients).  psi01 and tau may be NULL with zero coefficients; such a stream is not
+ * read.  The outputs are distinct and alias no input.                                                                       */
+int bk_nf1d_predict(bk_ctx* ctx, size_t n, const double* x0, const double* zeta, const double* psi01, const double* tau, int M,
+                    const double* alpha, const double* beta, const double* gamma, double* const* out);
+/* The whole of get_normal_form1d's computation (:281-337) at (x, params) for params[ipar]: the pass of bk_nf1d_dots, the pass
+ * of bk_nf1d_rhs, the two bordered solves and the pass of bk_nf1d_contract.  bopts->kind == 0 (BorderingBLS,
+ * src/LinearBorderSolver.jl:88-166): the systems share their matrix, so x1_k = J \ r_k run as one two-lane pair (as bk_gmres2)
+ * and x2 = J \ zeta* is solved ONCE -- three GMRES solves where the reference's two bls calls run four -- then
+ * Psi_k = x1_k - s_k x2 with s_k = <zeta, x1_k> / <zeta, x2>; check_precision / k / tol as bk_bls_bordering, every correction
+ * reusing x2.  kind == 1: two solves as bk_bls_matrixfree.  zeta and zeta* come normalised; unless |<zeta, zeta*> - 1| <= 1e-8
+ * the call is an error.  coef[5] = (a01, a02, b11, b20, b30); psi01 and psi20 are outputs, distinct from each other and from
+ * the inputs.  itlinear[3] = GMRES counts of the Psi01, Psi20 and J \ zeta* solves (kind 1: the two solves, 0).  J is
+ * singular by construction at these points, so an unconverged solve is no error (the reference logs it, :304, :334):
+ * *converged = the AND over all solves, and each unconverged one adds 1 to the context counter "nf1d_unconverged_solves".  */
+int bk_normal_form_1d(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar,
+                      const double* zeta, const double* zeta_star, const bk_bordering_opts* bopts, const bk_gmres_opts* lsopts,
+                      bk_precond* pl, double* psi01, double* psi20, double coef[5], int* converged, int itlinear[3]);
+
 #ifdef __cplusplus
 }
 #endif
