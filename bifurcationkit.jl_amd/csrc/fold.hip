@@ -5,7 +5,7 @@
 // The Swift-Hohenberg problems are symmetric (J' = J, :79-84), so the adjoint system is the same bordered solve with a and b
 // exchanged, and no solve at all when a and b are the same vector.  Their second derivative d2F(x, p)[dx1, dx2] =
 // h(u) dx1 dx2 and the parameter derivative of J, dJ/dp = diag(g_p(u)), are pointwise polynomials (fold_pw.h; fold_pw_kernel,
-// fold_contract_kernel below):
+// FoldContract below):
 //   BK_PDE_SH   h = 2 nu - 6 u                (examples/SH2d-fronts.jl:40)   g_l = 1,  g_nu = 2 u
 //   BK_PDE_SH1D h = 6 nu u - 20 u^3           (examples/SHpde_snaking.jl:26) g_lam = 1, g_nu = 3 u^2
 // so sigma_p = -<w, dJ/dp v> (:90-95), dpF (:88-89) and sigma_x . X (:153-157) are evaluated analytically: the reference's
@@ -38,61 +38,21 @@ __global__ void __launch_bounds__(kThreads) fold_pw_kernel(size_t n, const doubl
 // foldMALinearSolver (src/codim2/MinAugFold.jl:153-157) and sigma_p (:94-95) without materialising d2F(x, p)[X_k, v].
 // M + 1 partial sums per workgroup; the second stage (reduce_finish) keeps the fixed order, so the sums are bitwise the same
 // run to run and, all-reduced, on every rank.
-template <int M, int VEC, bool NTH>
-__global__ void __launch_bounds__(kThreads) fold_contract_kernel(size_t n, const double* __restrict__ pu,
-                                                                 const double* __restrict__ pv, const double* __restrict__ pw,
-                                                                 const double* __restrict__ X0, const double* __restrict__ X1,
-                                                                 const double* __restrict__ X2, FoldPoly P,
-                                                                 double* __restrict__ partials) {
-    double s[M + 1];
-#pragma unroll
-    for (int k = 0; k <= M; ++k) s[k] = 0.0;
-    const double* X[3] = {X0, X1, X2};
-    auto elem = [&](double uu, double vv, double ww, const double* xs) {
+template <int M>
+struct FoldContract {
+    static constexpr int NIN = 3 + M, NV = M + 1, U = 2, FIELDS = 1;
+    const double* in[NIN];          // u, v, w, X_0 .. X_{M-1}
+    FoldPoly P;
+    __device__ __forceinline__ void operator()(const double (&x)[NIN], double (&s)[NV]) const {
+        const double uu = x[0], vv = x[1], ww = x[2];
+        const double* xs = x + 3;
         const double t = ww * vv;
         const double th = t * fold_poly(P.h, uu);
 #pragma unroll
         for (int k = 0; k < M; ++k) s[k] = fma(th, xs[k], s[k]);
         s[M] = fma(t, fold_poly(P.g, uu), s[M]);
-    };
-    if (VEC == 2) {
-        stream_loop<2>(n >> 1, [&](auto uc, size_t i0, size_t st) {
-            constexpr int UU = decltype(uc)::value;
-            double2 uv[UU], vv[UU], wv[UU], xv[M > 0 ? M : 1][UU];
-#pragma unroll
-            for (int q = 0; q < UU; ++q) {
-                uv[q] = ld2<NTH>(pu, i0 + q * st);
-                vv[q] = ld2<NTH>(pv, i0 + q * st);
-                wv[q] = ld2<NTH>(pw, i0 + q * st);
-#pragma unroll
-                for (int k = 0; k < M; ++k) xv[k][q] = ld2<NTH>(X[k], i0 + q * st);
-            }
-#pragma unroll
-            for (int q = 0; q < UU; ++q) {
-                double xa[M > 0 ? M : 1], xb[M > 0 ? M : 1];
-#pragma unroll
-                for (int k = 0; k < M; ++k) { xa[k] = xv[k][q].x; xb[k] = xv[k][q].y; }
-                elem(uv[q].x, vv[q].x, wv[q].x, xa);
-                elem(uv[q].y, vv[q].y, wv[q].y, xb);
-            }
-        });
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            const size_t i = n - 1;
-            double xa[M > 0 ? M : 1];
-#pragma unroll
-            for (int k = 0; k < M; ++k) xa[k] = X[k][i];
-            elem(pu[i], pv[i], pw[i], xa);
-        }
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) {
-            double xa[M > 0 ? M : 1];
-#pragma unroll
-            for (int k = 0; k < M; ++k) xa[k] = X[k][i];
-            elem(pu[i], pv[i], pw[i], xa);
-        }
     }
-    block_sum_store<M + 1>(s, partials);
-}
+};
 
 static int v_fold_pw(bk_ctx* ctx, size_t n, const double* u, const double c[4], const double* x1, const double* x2, double* out) {
     if (n == 0) return 0;
@@ -107,24 +67,12 @@ static int v_fold_pw(bk_ctx* ctx, size_t n, const double* u, const double c[4], 
 static int v_fold_contract(bk_ctx* ctx, size_t n, const double* u, const double* v, const double* w, int m, const double* const* X,
                     const double h[4], const double g[4], double* out) {
     if (m < 0 || m > 3) return set_error(ctx, "v_fold_contract: 0 <= m <= 3 (got %d)", m);
-    FoldPoly P{};
-    for (int i = 0; i < 4; ++i) { P.h[i] = h[i]; P.g[i] = g[i]; }
-    const double* x[3] = {nullptr, nullptr, nullptr};
-    bool vec = aligned16(u) && aligned16(v) && aligned16(w);
-    for (int k = 0; k < m; ++k) { x[k] = X[k]; vec = vec && aligned16(X[k]); }
-    const bool nth = vec && nt_hint(ctx, n);
-    const int grid = grid_for(n, vec ? 4 : 1, kRedBlocks);        // stream_loop<2>: 2 x 16 B per lane per chunk
-    {
-        ProfScope ps(ctx, "fold_contract", 8.0 * n * (3 + m));
-        contract_dispatch(m, vec, nth, [&](auto M, auto V, auto NT) {
-            hipLaunchKernelGGL((fold_contract_kernel<decltype(M)::value, decltype(V)::value, decltype(NT)::value>), dim3(grid),
-                               dim3(kThreads), 0, ctx->stream, n, u, v, w, x[0], x[1], x[2], P, ctx->d_partials);
-        });
-        BK_HIP(ctx, hipGetLastError());
-    }
-    BK_TRY(reduce_finish(ctx, grid, m + 1, 0));
-    for (int k = 0; k <= m; ++k) out[k] = ctx->h_red[k];
-    return 0;
+    return count_dispatch<0, 3>(m, [&](auto M) {
+        FoldContract<decltype(M)::value> pass{{u, v, w}, {}};
+        for (int i = 0; i < 4; ++i) { pass.P.h[i] = h[i]; pass.P.g[i] = g[i]; }
+        for (int k = 0; k < m; ++k) pass.in[3 + k] = X[k];
+        return stream_reduce(ctx, "fold_contract", n, pass, out);
+    });
 }
 
 // ------------------------------------------------------------------ the formulation

@@ -49,24 +49,24 @@ __global__ void __launch_bounds__(kThreads) hopf_pw_kernel(size_t N, const doubl
     }
 }
 
-// field-1 base pointers of the streams of hopf_contract_kernel; field 2 of each starts N doubles later
-struct HopfStreams { const double *u, *vr, *vi, *wr, *wi, *x[3]; };
-
 // One pass over u, v = (vr, vi), w = (wr, wi) and M real vectors X_k:
 //   S_k = w^H d2F(u)[v, X_k] (k < M),   P = w^H dJ/dp(u) v,   Q = w^H v,
 // 2 (M + 2) partial sums per workgroup in the order (Re S_0, Im S_0, ..., Re P, Im P, Re Q, Im Q).  Per point the complex
 // 2-vector g = sum_f conj(w_f) H_f v does not depend on k, so S_k costs 4 FMAs per point.  The second stage (reduce_finish)
 // keeps the fixed order: the sums are bitwise the same run to run and, all-reduced, on every rank.
-template <int M, int VEC, bool NTH>
-__global__ void __launch_bounds__(kThreads) hopf_contract_kernel(size_t N, HopfStreams S, CglCoef c, double* __restrict__ partials) {
-    constexpr int NV = 2 * (M + 2);
-    double s[NV];
-#pragma unroll
-    for (int k = 0; k < NV; ++k) s[k] = 0.0;
+template <int M>
+struct HopfContract {
+    static constexpr int NIN = 2 * (5 + M), NV = 2 * (M + 2), U = 1, FIELDS = 2;
+    const double* in[NIN / FIELDS];  // u, vr, vi, wr, wi, X_0 .. X_{M-1}
+    CglCoef c;
     // one grid point: u = (u1, u2), v = (vr1 + i vi1, vr2 + i vi2), w likewise, X_k = (x1[k], x2[k])
-    auto elem = [&](double u1, double u2, double vr1, double vr2, double vi1, double vi2, double wr1, double wr2, double wi1,
-                    double wi2, const double* x1, const double* x2) {
+    __device__ __forceinline__ void operator()(const double (&x)[NIN], double (&s)[NV]) const {
+        const double u1 = x[0], u2 = x[1], vr1 = x[2], vr2 = x[3], vi1 = x[4], vi2 = x[5], wr1 = x[6], wr2 = x[7], wi1 = x[8],
+                     wi2 = x[9];
         if (M > 0) {
+            double x1[M > 0 ? M : 1], x2[M > 0 ? M : 1];
+#pragma unroll
+            for (int k = 0; k < M; ++k) { x1[k] = x[10 + 2 * k]; x2[k] = x[11 + 2 * k]; }
             double h[6];
             cgl_hess(c, u1, u2, h);
             // A_f = H_f vr, B_f = H_f vi
@@ -93,35 +93,8 @@ __global__ void __launch_bounds__(kThreads) hopf_contract_kernel(size_t N, HopfS
         s[2 * M + 1] += (wr1 * Br1 - wi1 * Ar1) + (wr2 * Br2 - wi2 * Ar2);
         s[2 * M + 2] += (wr1 * vr1 + wi1 * vi1) + (wr2 * vr2 + wi2 * vi2);
         s[2 * M + 3] += (wr1 * vi1 - wi1 * vr1) + (wr2 * vi2 - wi2 * vr2);
-    };
-    if (VEC == 2) {
-        // N even and every stream 16-B aligned in both fields (the launcher checks): N / 2 items, no ragged element
-        stream_loop<1>(N >> 1, [&](auto, size_t i, size_t) {
-            const double2 u1 = ld2<NTH>(S.u, i), u2 = ld2<NTH>(S.u + N, i);
-            const double2 vr1 = ld2<NTH>(S.vr, i), vr2 = ld2<NTH>(S.vr + N, i);
-            const double2 vi1 = ld2<NTH>(S.vi, i), vi2 = ld2<NTH>(S.vi + N, i);
-            const double2 wr1 = ld2<NTH>(S.wr, i), wr2 = ld2<NTH>(S.wr + N, i);
-            const double2 wi1 = ld2<NTH>(S.wi, i), wi2 = ld2<NTH>(S.wi + N, i);
-            double2 x1[M > 0 ? M : 1], x2[M > 0 ? M : 1];
-#pragma unroll
-            for (int k = 0; k < M; ++k) { x1[k] = ld2<NTH>(S.x[k], i); x2[k] = ld2<NTH>(S.x[k] + N, i); }
-            double xa1[M > 0 ? M : 1], xa2[M > 0 ? M : 1], xb1[M > 0 ? M : 1], xb2[M > 0 ? M : 1];
-#pragma unroll
-            for (int k = 0; k < M; ++k) { xa1[k] = x1[k].x; xa2[k] = x2[k].x; xb1[k] = x1[k].y; xb2[k] = x2[k].y; }
-            elem(u1.x, u2.x, vr1.x, vr2.x, vi1.x, vi2.x, wr1.x, wr2.x, wi1.x, wi2.x, xa1, xa2);
-            elem(u1.y, u2.y, vr1.y, vr2.y, vi1.y, vi2.y, wr1.y, wr2.y, wi1.y, wi2.y, xb1, xb2);
-        });
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < N; i += (size_t)gridDim.x * kThreads) {
-            double xa1[M > 0 ? M : 1], xa2[M > 0 ? M : 1];
-#pragma unroll
-            for (int k = 0; k < M; ++k) { xa1[k] = S.x[k][i]; xa2[k] = S.x[k][i + N]; }
-            elem(S.u[i], S.u[i + N], S.vr[i], S.vr[i + N], S.vi[i], S.vi[i + N], S.wr[i], S.wr[i + N], S.wi[i], S.wi[i + N],
-                 xa1, xa2);
-        }
     }
-    block_sum_store<NV>(s, partials);
-}
+};
 
 static int v_hopf_pw(bk_ctx* ctx, size_t n, const double* u, const CglCoef& c, const double* x1, const double* x2, double* out) {
     const size_t N = n / 2;
@@ -136,25 +109,11 @@ static int v_hopf_pw(bk_ctx* ctx, size_t n, const double* u, const CglCoef& c, c
 static int v_hopf_contract(bk_ctx* ctx, size_t n, const double* u, const double* vr, const double* vi, const double* wr,
                            const double* wi, int m, const double* const* X, const CglCoef& c, double* out) {
     if (m < 0 || m > 3) return set_error(ctx, "v_hopf_contract: 0 <= m <= 3 (got %d)", m);
-    const size_t N = n / 2;
-    HopfStreams S{u, vr, vi, wr, wi, {nullptr, nullptr, nullptr}};
-    auto al = [N](const double* p) { return aligned16(p) && aligned16(p + N); };
-    bool vec = (N % 2 == 0) && al(u) && al(vr) && al(vi) && al(wr) && al(wi);
-    for (int k = 0; k < m; ++k) { S.x[k] = X[k]; vec = vec && al(X[k]); }
-    const bool nth = vec && nt_hint(ctx, n);
-    const int grid = grid_for(N, vec ? 2 : 1, kRedBlocks);
-    {
-        ProfScope ps(ctx, "hopf_contract", 8.0 * n * (5 + m));
-        contract_dispatch(m, vec, nth, [&](auto M, auto V, auto NT) {
-            hipLaunchKernelGGL((hopf_contract_kernel<decltype(M)::value, decltype(V)::value, decltype(NT)::value>), dim3(grid),
-                               dim3(kThreads), 0, ctx->stream, N, S, c, ctx->d_partials);
-        });
-        BK_HIP(ctx, hipGetLastError());
-    }
-    const int nv = 2 * (m + 2);
-    BK_TRY(reduce_finish(ctx, grid, nv, 0));
-    for (int k = 0; k < nv; ++k) out[k] = ctx->h_red[k];
-    return 0;
+    return count_dispatch<0, 3>(m, [&](auto M) {
+        HopfContract<decltype(M)::value> pass{{u, vr, vi, wr, wi}, c};
+        for (int k = 0; k < m; ++k) pass.in[5 + k] = X[k];
+        return stream_reduce(ctx, "hopf_contract", n / 2, pass, out);
+    });
 }
 
 // ------------------------------------------------------------------ the formulation

@@ -49,18 +49,19 @@ __global__ void __launch_bounds__(kThreads) hopf_d3_kernel(size_t N, const doubl
     }
 }
 
-__device__ __forceinline__ void st2(double* p, size_t i, double a, double b) { reinterpret_cast<double2*>(p)[i] = make_double2(a, b); }
-
 // One pass over u and zeta = x + i y that writes the right-hand sides of the Psi200 and Psi110 solves:
 //   r20 = d2F[zeta, zeta] / 2 = (x'Hx - y'Hy) / 2 + i x'Hy,     r11 = s11 d2F[zeta, conj zeta] = s11 (x'Hx + y'Hy)
 // per field (s11 = -1 inside bk_hopf_normal_form, whose solve wants the negated vector).  3 read and 3 write streams.
-template <int VEC, bool NTH>
-__global__ void __launch_bounds__(kThreads) hopf_nf_rhs_kernel(size_t N, const double* __restrict__ u, const double* __restrict__ zr,
-                                                               const double* __restrict__ zi, CglCoef c, double s11,
-                                                               double* __restrict__ r20r, double* __restrict__ r20i,
-                                                               double* __restrict__ r11) {
+struct HopfNfRhs {
+    static constexpr int NIN = 6, NOUT = 6, U = 1, FIELDS = 2;
+    static constexpr bool JOINT = true;
+    const double* in[NIN / FIELDS];     // u, zr, zi
+    double* out[NOUT / FIELDS];         // r20r, r20i, r11
+    CglCoef c;
+    double s11;
     // o = (r20r_1, r20r_2, r20i_1, r20i_2, r11_1, r11_2) of one grid point
-    auto elem = [&](double u1, double u2, double x1, double x2, double y1, double y2, double o[6]) {
+    __device__ __forceinline__ void operator()(const double (&x)[NIN], double (&o)[NOUT]) const {
+        const double u1 = x[0], u2 = x[1], x1 = x[2], x2 = x[3], y1 = x[4], y2 = x[5];
         double h[6];
         cgl_hess(c, u1, u2, h);
 #pragma unroll
@@ -73,33 +74,8 @@ __global__ void __launch_bounds__(kThreads) hopf_nf_rhs_kernel(size_t N, const d
             o[2 + f] = xy;
             o[4 + f] = s11 * (xx + yy);
         }
-    };
-    if (VEC == 2) {
-        // N even and every stream 16-B aligned in both fields (the launcher checks)
-        stream_loop<1>(N >> 1, [&](auto, size_t i, size_t) {
-            const double2 u1 = ld2<NTH>(u, i), u2 = ld2<NTH>(u + N, i);
-            const double2 x1 = ld2<NTH>(zr, i), x2 = ld2<NTH>(zr + N, i);
-            const double2 y1 = ld2<NTH>(zi, i), y2 = ld2<NTH>(zi + N, i);
-            double a[6], b[6];
-            elem(u1.x, u2.x, x1.x, x2.x, y1.x, y2.x, a);
-            elem(u1.y, u2.y, x1.y, x2.y, y1.y, y2.y, b);
-            st2(r20r, i, a[0], b[0]); st2(r20r + N, i, a[1], b[1]);
-            st2(r20i, i, a[2], b[2]); st2(r20i + N, i, a[3], b[3]);
-            st2(r11, i, a[4], b[4]); st2(r11 + N, i, a[5], b[5]);
-        });
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < N; i += (size_t)gridDim.x * kThreads) {
-            double a[6];
-            elem(u[i], u[i + N], zr[i], zr[i + N], zi[i], zi[i + N], a);
-            r20r[i] = a[0]; r20r[i + N] = a[1];
-            r20i[i] = a[2]; r20i[i + N] = a[3];
-            r11[i] = a[4]; r11[i + N] = a[5];
-        }
     }
-}
-
-// field-1 base pointers of the streams of hopf_nf_contract_kernel; field 2 of each starts N doubles later
-struct NfStreams { const double *u, *zr, *zi, *sr, *si, *p, *q, *gr, *gi; };
+};
 
 // One pass over u, zeta = x + i y (zr, zi), zeta* (sr, si), Psi001 = p, Psi110 = q, Psi200 = gr + i gi: four partial sums per
 // workgroup, (Re a, Im a, Re b, Im b).  Every term is zeta or conj zeta against a per-point vector of field f,
@@ -108,12 +84,15 @@ struct NfStreams { const double *u, *zr, *zi, *sr, *si, *p, *q, *gr, *gi; };
 // with s_f = T_f : (x x' + y y'), because d3F[zeta, zeta, conj zeta] = zeta . s_f  (H_f conj(zeta) = conj(H_f zeta)), and
 //   a += conj(av_f) zeta*_f,   b += conj(bv_f) zeta*_f.
 // The second stage (reduce_finish) keeps the fixed order: the sums are bitwise the same run to run and, all-reduced, on every rank.
-template <int VEC, bool NTH>
-__global__ void __launch_bounds__(kThreads) hopf_nf_contract_kernel(size_t N, NfStreams S, CglCoef c, double* __restrict__ partials) {
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    // one grid point; the second index of every argument is the field
-    auto elem = [&](double u1, double u2, double x1, double x2, double y1, double y2, double sr1, double sr2, double si1,
-                    double si2, double p1, double p2, double q1, double q2, double gr1, double gr2, double gi1, double gi2) {
+struct HopfNfContract {
+    static constexpr int NIN = 18, NV = 4, U = 1, FIELDS = 2;
+    const double* in[NIN / FIELDS];     // u, zr, zi, sr, si, p, q, gr, gi
+    CglCoef c;
+    // one grid point; the second index of every name is the field
+    __device__ __forceinline__ void operator()(const double (&v)[NIN], double (&s)[NV]) const {
+        const double u1 = v[0], u2 = v[1], x1 = v[2], x2 = v[3], y1 = v[4], y2 = v[5], sr1 = v[6], sr2 = v[7], si1 = v[8],
+                     si2 = v[9], p1 = v[10], p2 = v[11], q1 = v[12], q2 = v[13], gr1 = v[14], gr2 = v[15], gi1 = v[16],
+                     gi2 = v[17];
         double h[6], d[4], t[8];
         cgl_hess(c, u1, u2, h);
         cgl_djdp(c.ipar, u1, u2, d);
@@ -137,65 +116,30 @@ __global__ void __launch_bounds__(kThreads) hopf_nf_contract_kernel(size_t N, Nf
             s[2] += bvr * sr[f] + bvi * si[f];
             s[3] += bvr * si[f] - bvi * sr[f];
         }
-    };
-    if (VEC == 2) {
-        // N even and every stream 16-B aligned in both fields (the launcher checks): N / 2 items, no ragged element
-        stream_loop<1>(N >> 1, [&](auto, size_t i, size_t) {
-            const double2 u1 = ld2<NTH>(S.u, i), u2 = ld2<NTH>(S.u + N, i);
-            const double2 x1 = ld2<NTH>(S.zr, i), x2 = ld2<NTH>(S.zr + N, i);
-            const double2 y1 = ld2<NTH>(S.zi, i), y2 = ld2<NTH>(S.zi + N, i);
-            const double2 a1 = ld2<NTH>(S.sr, i), a2 = ld2<NTH>(S.sr + N, i);
-            const double2 b1 = ld2<NTH>(S.si, i), b2 = ld2<NTH>(S.si + N, i);
-            const double2 p1 = ld2<NTH>(S.p, i), p2 = ld2<NTH>(S.p + N, i);
-            const double2 q1 = ld2<NTH>(S.q, i), q2 = ld2<NTH>(S.q + N, i);
-            const double2 g1 = ld2<NTH>(S.gr, i), g2 = ld2<NTH>(S.gr + N, i);
-            const double2 k1 = ld2<NTH>(S.gi, i), k2 = ld2<NTH>(S.gi + N, i);
-            elem(u1.x, u2.x, x1.x, x2.x, y1.x, y2.x, a1.x, a2.x, b1.x, b2.x, p1.x, p2.x, q1.x, q2.x, g1.x, g2.x, k1.x, k2.x);
-            elem(u1.y, u2.y, x1.y, x2.y, y1.y, y2.y, a1.y, a2.y, b1.y, b2.y, p1.y, p2.y, q1.y, q2.y, g1.y, g2.y, k1.y, k2.y);
-        });
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < N; i += (size_t)gridDim.x * kThreads)
-            elem(S.u[i], S.u[i + N], S.zr[i], S.zr[i + N], S.zi[i], S.zi[i + N], S.sr[i], S.sr[i + N], S.si[i], S.si[i + N],
-                 S.p[i], S.p[i + N], S.q[i], S.q[i + N], S.gr[i], S.gr[i + N], S.gi[i], S.gi[i + N]);
     }
-    block_sum_store<4>(s, partials);
-}
-
-// M <= kOrbit phases of the predictor's orbit per launch: the coefficients of A_m = amp e^{i t_m} as the kernel applies them
-constexpr int kOrbit = 8;
-struct OrbitArgs {
-    double c1r[kOrbit], c1i[kOrbit];     // 2 Re A_m, -2 Im A_m          (2 Re(zeta A) = 2 Re A zr - 2 Im A zi)
-    double cq[kOrbit];                   // |A_m|^2
-    double c2r[kOrbit], c2i[kOrbit];     // 2 Re A_m^2, -2 Im A_m^2
-    double* out[kOrbit];
 };
 
-// out_m = x0 + ds Psi001 + 2 Re(zeta A_m) + |A_m|^2 Psi110 + 2 Re(A_m^2 Psi200)  (src/NormalForms.jl:1262-1271) for m < M in one
-// pass: the seven inputs are read once, n elements each (the vectors are walked flat, both fields alike)
-template <int M, int VEC, bool NTH>
-__global__ void __launch_bounds__(kThreads) hopf_orbit_kernel(size_t n, const double* __restrict__ x0, const double* __restrict__ zr,
-                                                              const double* __restrict__ zi, const double* __restrict__ p,
-                                                              const double* __restrict__ q, const double* __restrict__ gr,
-                                                              const double* __restrict__ gi, double ds, OrbitArgs A) {
-    auto elem = [&](int m, double x, double a, double b, double pp, double qq, double g, double k) {
-        return ((((x + ds * pp) + A.c1r[m] * a) + A.c1i[m] * b) + A.cq[m] * qq) + (A.c2r[m] * g + A.c2i[m] * k);
-    };
-    if (VEC == 2) {
-        stream_loop<1>(n >> 1, [&](auto, size_t i, size_t) {
-            const double2 x = ld2<NTH>(x0, i), a = ld2<NTH>(zr, i), b = ld2<NTH>(zi, i), pp = ld2<NTH>(p, i), qq = ld2<NTH>(q, i),
-                          g = ld2<NTH>(gr, i), k = ld2<NTH>(gi, i);
+// out_m = x0 + ds Psi001 + 2 Re(zeta A_m) + |A_m|^2 Psi110 + 2 Re(A_m^2 Psi200)  (src/NormalForms.jl:1262-1271) for m < M <= kOrbit
+// phases of the predictor's orbit in one pass: the seven inputs are read once, n elements each (the vectors are walked flat, both
+// fields alike).  The coefficients of A_m = amp e^{i t_m} are stored as the pass applies them.
+constexpr int kOrbit = 8;
+template <int M>
+struct HopfOrbit {
+    static constexpr int NIN = 7, NOUT = M, U = 1, FIELDS = 1;
+    static constexpr bool JOINT = false;
+    const double* in[NIN];          // x0, zr, zi, Psi001, Psi110, Re Psi200, Im Psi200
+    double* out[NOUT];
+    double ds;
+    double c1r[M], c1i[M];          // 2 Re A_m, -2 Im A_m          (2 Re(zeta A) = 2 Re A zr - 2 Im A zi)
+    double cq[M];                   // |A_m|^2
+    double c2r[M], c2i[M];          // 2 Re A_m^2, -2 Im A_m^2
+    __device__ __forceinline__ void operator()(const double (&v)[NIN], double (&o)[NOUT]) const {
+        const double x = v[0], a = v[1], b = v[2], pp = v[3], qq = v[4], g = v[5], k = v[6];
 #pragma unroll
-            for (int m = 0; m < M; ++m)
-                st2(A.out[m], i, elem(m, x.x, a.x, b.x, pp.x, qq.x, g.x, k.x), elem(m, x.y, a.y, b.y, pp.y, qq.y, g.y, k.y));
-        });
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) {
-            const double x = x0[i], a = zr[i], b = zi[i], pp = p[i], qq = q[i], g = gr[i], k = gi[i];
-#pragma unroll
-            for (int m = 0; m < M; ++m) A.out[m][i] = elem(m, x, a, b, pp, qq, g, k);
-        }
+        for (int m = 0; m < M; ++m)
+            o[m] = ((((x + ds * pp) + c1r[m] * a) + c1i[m] * b) + cq[m] * qq) + (c2r[m] * g + c2i[m] * k);
     }
-}
+};
 
 // ------------------------------------------------------------------ launchers
 int v_hopf_d3(bk_ctx* ctx, size_t n, const double* u, const CglCoef& c, const double* x1, const double* x2, const double* x3,
@@ -211,79 +155,32 @@ int v_hopf_d3(bk_ctx* ctx, size_t n, const double* u, const CglCoef& c, const do
 // r20 = d2F[zeta, zeta] / 2 as (re, im), r11 = s11 d2F[zeta, conj zeta]; n = 2 N, the local length of both fields
 int v_hopf_nf_rhs(bk_ctx* ctx, size_t n, const double* u, const CglCoef& c, const double* zr, const double* zi, double s11,
                   double* r20r, double* r20i, double* r11) {
-    const size_t N = n / 2;
-    if (N == 0) return 0;
-    auto al = [N](const double* p) { return aligned16(p) && aligned16(p + N); };
-    const bool vec = (N % 2 == 0) && al(u) && al(zr) && al(zi) && al(r20r) && al(r20i) && al(r11);
-    const bool nth = vec && nt_hint(ctx, n);
-    const int grid = grid_for(N, vec ? 2 : 1, 4096);
-    ProfScope ps(ctx, "hopf_nf_rhs", 8.0 * n * 6);
-    load_path_dispatch(vec, nth, [&](auto V, auto NT) {
-        hipLaunchKernelGGL((hopf_nf_rhs_kernel<decltype(V)::value, decltype(NT)::value>), dim3(grid), dim3(kThreads), 0,
-                           ctx->stream, N, u, zr, zi, c, s11, r20r, r20i, r11);
-    });
-    BK_HIP(ctx, hipGetLastError());
-    return 0;
+    return stream_write(ctx, "hopf_nf_rhs", n / 2, HopfNfRhs{{u, zr, zi}, {r20r, r20i, r11}, c, s11});
 }
 
-// out[4] = (Re a, Im a, Re b, Im b)
-int v_hopf_nf_contract(bk_ctx* ctx, size_t n, const NfStreams& S, const CglCoef& c, double* out) {
-    const size_t N = n / 2;
-    auto al = [N](const double* p) { return aligned16(p) && aligned16(p + N); };
-    const bool vec = (N % 2 == 0) && al(S.u) && al(S.zr) && al(S.zi) && al(S.sr) && al(S.si) && al(S.p) && al(S.q) && al(S.gr) &&
-                     al(S.gi);
-    const bool nth = vec && nt_hint(ctx, n);
-    const int grid = grid_for(N, vec ? 2 : 1, kRedBlocks);
-    {
-        ProfScope ps(ctx, "hopf_nf_contract", 8.0 * n * 9);
-        load_path_dispatch(vec, nth, [&](auto V, auto NT) {
-            hipLaunchKernelGGL((hopf_nf_contract_kernel<decltype(V)::value, decltype(NT)::value>), dim3(grid), dim3(kThreads), 0,
-                               ctx->stream, N, S, c, ctx->d_partials);
-        });
-        BK_HIP(ctx, hipGetLastError());
-    }
-    BK_TRY(reduce_finish(ctx, grid, 4, 0));
-    for (int k = 0; k < 4; ++k) out[k] = ctx->h_red[k];
-    return 0;
+// out[4] = (Re a, Im a, Re b, Im b); S = u, zr, zi, sr, si, p, q, gr, gi
+int v_hopf_nf_contract(bk_ctx* ctx, size_t n, const double* const (&S)[9], const CglCoef& c, double* out) {
+    HopfNfContract pass{{}, c};
+    for (int k = 0; k < 9; ++k) pass.in[k] = S[k];
+    return stream_reduce(ctx, "hopf_nf_contract", n / 2, pass, out);
 }
 
-// m <= kOrbit phases t[0..m) into A.out[0..m)
+// m <= kOrbit phases t[0..m) into out[0..m)
 int v_hopf_orbit(bk_ctx* ctx, size_t n, const double* x0, const double* zr, const double* zi, const double* p, const double* q,
                  const double* gr, const double* gi, double ds, double amp, int m, const double* t, double* const* out) {
-    OrbitArgs A{};
-    bool vec = (n % 2 == 0) && aligned16(x0) && aligned16(zr) && aligned16(zi) && aligned16(p) && aligned16(q) && aligned16(gr) &&
-               aligned16(gi);
-    for (int k = 0; k < m; ++k) {
-        const double a2 = amp * amp;
-        A.c1r[k] = 2.0 * (amp * std::cos(t[k]));
-        A.c1i[k] = -2.0 * (amp * std::sin(t[k]));
-        A.cq[k] = a2;
-        A.c2r[k] = 2.0 * (a2 * std::cos(2.0 * t[k]));
-        A.c2i[k] = -2.0 * (a2 * std::sin(2.0 * t[k]));
-        A.out[k] = out[k];
-        vec = vec && aligned16(out[k]);
-    }
-    const bool nth = vec && nt_hint(ctx, n);
-    const int grid = grid_for(n, vec ? 2 : 1, 4096);
-    ProfScope ps(ctx, "hopf_orbit", 8.0 * n * (7 + m));
-    auto variant = [&](auto M) {
-        load_path_dispatch(vec, nth, [&](auto V, auto NT) {
-            hipLaunchKernelGGL((hopf_orbit_kernel<decltype(M)::value, decltype(V)::value, decltype(NT)::value>), dim3(grid),
-                               dim3(kThreads), 0, ctx->stream, n, x0, zr, zi, p, q, gr, gi, ds, A);
-        });
-    };
-    switch (m) {
-        case 1: variant(std::integral_constant<int, 1>{}); break;
-        case 2: variant(std::integral_constant<int, 2>{}); break;
-        case 3: variant(std::integral_constant<int, 3>{}); break;
-        case 4: variant(std::integral_constant<int, 4>{}); break;
-        case 5: variant(std::integral_constant<int, 5>{}); break;
-        case 6: variant(std::integral_constant<int, 6>{}); break;
-        case 7: variant(std::integral_constant<int, 7>{}); break;
-        default: variant(std::integral_constant<int, 8>{}); break;
-    }
-    BK_HIP(ctx, hipGetLastError());
-    return 0;
+    return count_dispatch<1, kOrbit>(m, [&](auto M) {
+        HopfOrbit<decltype(M)::value> pass{{x0, zr, zi, p, q, gr, gi}, {}, ds};
+        for (int k = 0; k < m; ++k) {
+            const double a2 = amp * amp;
+            pass.c1r[k] = 2.0 * (amp * std::cos(t[k]));
+            pass.c1i[k] = -2.0 * (amp * std::sin(t[k]));
+            pass.cq[k] = a2;
+            pass.c2r[k] = 2.0 * (a2 * std::cos(2.0 * t[k]));
+            pass.c2i[k] = -2.0 * (a2 * std::sin(2.0 * t[k]));
+            pass.out[k] = out[k];
+        }
+        return stream_write(ctx, "hopf_orbit", n, pass);
+    });
 }
 
 }  // namespace
@@ -324,7 +221,7 @@ int bk_hopf_nf_contract(bk_problem* prob, const double* u, const double* params,
         return -1;
     CglCoef c;
     BK_TRY(hopf_coef(prob, params, nparams, ipar, &c));
-    const NfStreams S{u, z_re, z_im, zs_re, zs_im, psi001, psi110, psi200_re, psi200_im};
+    const double* const S[9] = {u, z_re, z_im, zs_re, zs_im, psi001, psi110, psi200_re, psi200_im};
     return v_hopf_nf_contract(prob->ctx, prob->nloc, S, c, out);
 }
 
@@ -368,7 +265,7 @@ int bk_hopf_normal_form(bk_ctx* ctx, bk_problem* prob, const double* x, const do
     int cv2 = 0, it2 = 0;
     BK_TRY(bk_gmres_cshift(ctx, jp.J, r20r, r20i, psi200_re, psi200_im, 0.0, 2.0 * omega, -1.0, lsopts, pl, &cv2, &it2, nullptr));
     ctx->diag.hopf_nf_unconverged += (r0.converged ? 0.0 : 1.0) + (r1.converged ? 0.0 : 1.0) + (cv2 ? 0.0 : 1.0);
-    const NfStreams S{x, z_re, z_im, zs_re, zs_im, psi001, psi110, psi200_re, psi200_im};
+    const double* const S[9] = {x, z_re, z_im, zs_re, zs_im, psi001, psi110, psi200_re, psi200_im};
     BK_TRY(v_hopf_nf_contract(ctx, n, S, c, ab));
     if (converged) *converged = r0.converged & r1.converged & cv2;
     if (itlinear) { itlinear[0] = r0.niter; itlinear[1] = r1.niter; itlinear[2] = it2; }

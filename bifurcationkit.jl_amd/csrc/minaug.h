@@ -1,59 +1,16 @@
-// What the minimally augmented fold (fold.hip) and Hopf (hopf.hip) formulations share: the reduction epilogue and the
-// M x variant dispatch of their contraction kernels, the J \ rhs_k, J \ dpF solves of their linear solvers, the checks of the
-// bk_*_linsolve entries and the Newton loop of bk_newton_fold / bk_newton_hopf.  What differs between them -- the pointwise
-// tensors, the contractions, the bordered solves, the norms and the 1 x 1 or 2 x 2 scalar system -- stays in the two files.
+// What the minimally augmented fold (fold.hip) and Hopf (hopf.hip) formulations share: the J \ rhs_k, J \ dpF solves of their
+// linear solvers, the checks of the bk_*_linsolve entries and the Newton loop of bk_newton_fold / bk_newton_hopf.  What differs
+// between them -- the pointwise tensors, the contractions, the bordered solves, the norms and the 1 x 1 or 2 x 2 scalar system --
+// stays in the two files.  JPair and minaug_check also serve the normal forms (hopf_nf.hip, nf1d.hip).
 // Internal header.
 #pragma once
 #include <cmath>
-#include <type_traits>
 
 #include "common.h"
 #include "ops.h"
-#include "stream.h"
 
 namespace bk {
 namespace {
-
-// ------------------------------------------------------------------ contraction kernels
-// Epilogue of a contraction kernel: NV sums per lane -> NV partial sums of the workgroup, partials[blockIdx.x * NV + k].  Wave
-// sums, then the four waves in the fixed order (0 + 1) + (2 + 3); the second stage (reduce_finish) keeps a fixed order too.
-template <int NV>
-__device__ __forceinline__ void block_sum_store(const double (&s)[NV], double* partials) {
-    __shared__ double sm[NV][4];
-    const int lane = threadIdx.x & 63, wv_ = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const double t = wave_sum(s[k]);
-        if (lane == 0) sm[k][wv_] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        const int k = threadIdx.x;
-        partials[(size_t)blockIdx.x * NV + k] = (sm[k][0] + sm[k][1]) + (sm[k][2] + sm[k][3]);
-    }
-}
-
-// launch(VEC, NTH) as integral constants: the load path of a streaming kernel template <..., int VEC, bool NTH> -- non-temporal
-// 16-byte loads (nth), 16-byte loads (vec) or element by element (fold.hip, hopf.hip, hopf_nf.hip, nf1d.hip)
-template <class Launch>
-void load_path_dispatch(bool vec, bool nth, Launch&& launch) {
-    if (nth) launch(std::integral_constant<int, 2>{}, std::true_type{});
-    else if (vec) launch(std::integral_constant<int, 2>{}, std::false_type{});
-    else launch(std::integral_constant<int, 1>{}, std::false_type{});
-}
-
-// launch(M, VEC, NTH) as integral constants for a kernel template <int M, int VEC, bool NTH>: m = 0..3 extra vectors, each on
-// the load path of load_path_dispatch
-template <class Launch>
-void contract_dispatch(int m, bool vec, bool nth, Launch&& launch) {
-    auto variant = [&](auto M) { load_path_dispatch(vec, nth, [&](auto V, auto NT) { launch(M, V, NT); }); };
-    switch (m) {
-        case 0: variant(std::integral_constant<int, 0>{}); break;
-        case 1: variant(std::integral_constant<int, 1>{}); break;
-        case 2: variant(std::integral_constant<int, 2>{}); break;
-        default: variant(std::integral_constant<int, 3>{}); break;
-    }
-}
 
 // ------------------------------------------------------------------ the formulation
 int minaug_check(bk_ctx* ctx, bk_problem* prob, const char* what) {

@@ -41,112 +41,58 @@ __global__ void __launch_bounds__(kThreads) nf1d_d3_kernel(size_t n, const doubl
 //   s0 = sum f(u) zs = a01,   s1 = sum ((h(u) z) z) zs = b20,   s2 = sum z zs = <zeta, zeta*>.
 // P = (h, g) of d2F and dJ/dp, Q = (t, f) of d3F and dF/dp.  zs may be the same vector as z (both are only read).  The second
 // stage (reduce_finish) keeps the fixed order: the sums are bitwise the same run to run and, all-reduced, on every rank.
-template <int VEC, bool NTH>
-__global__ void __launch_bounds__(kThreads) nf1d_dots_kernel(size_t n, const double* pu, const double* pz, const double* pzs,
-                                                             FoldPoly P, FoldPoly Q, double* __restrict__ partials) {
-    double s[3] = {0.0, 0.0, 0.0};
-    auto elem = [&](double u, double z, double zs) {
+struct Nf1dDots {
+    static constexpr int NIN = 3, NV = 3, U = 2, FIELDS = 1;
+    const double* in[NIN];          // u, z, zs
+    FoldPoly P, Q;
+    __device__ __forceinline__ void operator()(const double (&x)[NIN], double (&s)[NV]) const {
+        const double u = x[0], z = x[1], zs = x[2];
         s[0] += fold_poly(Q.g, u) * zs;
         s[1] += ((fold_poly(P.h, u) * z) * z) * zs;
         s[2] += z * zs;
-    };
-    if (VEC == 2) {
-        stream_loop<2>(n >> 1, [&](auto uc, size_t i0, size_t st) {
-            constexpr int UU = decltype(uc)::value;
-            double2 uv[UU], zv[UU], sv[UU];
-#pragma unroll
-            for (int q = 0; q < UU; ++q) {
-                uv[q] = ld2<NTH>(pu, i0 + q * st);
-                zv[q] = ld2<NTH>(pz, i0 + q * st);
-                sv[q] = ld2<NTH>(pzs, i0 + q * st);
-            }
-#pragma unroll
-            for (int q = 0; q < UU; ++q) {
-                elem(uv[q].x, zv[q].x, sv[q].x);
-                elem(uv[q].y, zv[q].y, sv[q].y);
-            }
-        });
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) elem(pu[n - 1], pz[n - 1], pzs[n - 1]);
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads)
-            elem(pu[i], pz[i], pzs[i]);
     }
-    block_sum_store<3>(s, partials);
-}
-
-__device__ __forceinline__ void st2(double* p, size_t i, double a, double b) { reinterpret_cast<double2*>(p)[i] = make_double2(a, b); }
+};
 
 // One pass over u and zeta = z that writes the two projected right-hand sides of the bordered solves,
 //   r1 = E(-dpF) = a01 z - f(u),   r2 = E(-d2F[zeta, zeta]) = b20 z - (h(u) z) z.      2 read and 2 write streams.
-template <int VEC, bool NTH>
-__global__ void __launch_bounds__(kThreads) nf1d_rhs_kernel(size_t n, const double* __restrict__ pu, const double* __restrict__ pz,
-                                                            FoldPoly P, FoldPoly Q, double a01, double b20,
-                                                            double* __restrict__ r1, double* __restrict__ r2) {
-    auto e1 = [&](double u, double z) { return a01 * z - fold_poly(Q.g, u); };
-    auto e2 = [&](double u, double z) { return b20 * z - (fold_poly(P.h, u) * z) * z; };
-    if (VEC == 2) {
-        stream_loop<1>(n >> 1, [&](auto, size_t i, size_t) {
-            const double2 u = ld2<NTH>(pu, i), z = ld2<NTH>(pz, i);
-            st2(r1, i, e1(u.x, z.x), e1(u.y, z.y));
-            st2(r2, i, e2(u.x, z.x), e2(u.y, z.y));
-        });
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-            r1[n - 1] = e1(pu[n - 1], pz[n - 1]);
-            r2[n - 1] = e2(pu[n - 1], pz[n - 1]);
-        }
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) {
-            r1[i] = e1(pu[i], pz[i]);
-            r2[i] = e2(pu[i], pz[i]);
-        }
+struct Nf1dRhs {
+    static constexpr int NIN = 2, NOUT = 2, U = 1, FIELDS = 1;
+    static constexpr bool JOINT = false;
+    const double* in[NIN];          // u, z
+    double* out[NOUT];              // r1, r2
+    FoldPoly P, Q;
+    double a01, b20;
+    __device__ __forceinline__ void operator()(const double (&x)[NIN], double (&o)[NOUT]) const {
+        const double u = x[0], z = x[1];
+        o[0] = a01 * z - fold_poly(Q.g, u);
+        o[1] = b20 * z - (fold_poly(P.h, u) * z) * z;
     }
-}
+};
 
 // One pass over u, zeta = z, zeta* = zs, Psi01 = p, Psi20 = q: three partial sums per workgroup,
 //   s0 = sum (g z + (h z) p) zs                  = b11
 //   s1 = sum (2 (g p) + (h p) p) zs              = a02      (d2F/dp2 = 0)
 //   s2 = sum (((t z) z) z + 3 ((h z) q)) zs      = b30
 // without materialising dJ/dp zeta, dJ/dp Psi01, the three d2F and d3F[zeta, zeta, zeta].
-template <int VEC, bool NTH>
-__global__ void __launch_bounds__(kThreads) nf1d_contract_kernel(size_t n, const double* pu, const double* pz, const double* pzs,
-                                                                 const double* pp, const double* pq, FoldPoly P, FoldPoly Q,
-                                                                 double* __restrict__ partials) {
-    double s[3] = {0.0, 0.0, 0.0};
-    auto elem = [&](double u, double z, double zs, double p, double q) {
+struct Nf1dContract {
+    static constexpr int NIN = 5, NV = 3, U = 2, FIELDS = 1;
+    const double* in[NIN];          // u, z, zs, p, q
+    FoldPoly P, Q;
+    __device__ __forceinline__ void operator()(const double (&x)[NIN], double (&s)[NV]) const {
+        const double u = x[0], z = x[1], zs = x[2], p = x[3], q = x[4];
         const double h = fold_poly(P.h, u), g = fold_poly(P.g, u), t = fold_poly(Q.h, u);
         const double hz = h * z;
         s[0] += (g * z + hz * p) * zs;
         s[1] += (2.0 * (g * p) + (h * p) * p) * zs;
         s[2] += (((t * z) * z) * z + 3.0 * (hz * q)) * zs;
-    };
-    if (VEC == 2) {
-        stream_loop<2>(n >> 1, [&](auto uc, size_t i0, size_t st) {
-            constexpr int UU = decltype(uc)::value;
-            double2 uv[UU], zv[UU], sv[UU], pv[UU], qv[UU];
-#pragma unroll
-            for (int k = 0; k < UU; ++k) {
-                uv[k] = ld2<NTH>(pu, i0 + k * st);
-                zv[k] = ld2<NTH>(pz, i0 + k * st);
-                sv[k] = ld2<NTH>(pzs, i0 + k * st);
-                pv[k] = ld2<NTH>(pp, i0 + k * st);
-                qv[k] = ld2<NTH>(pq, i0 + k * st);
-            }
-#pragma unroll
-            for (int k = 0; k < UU; ++k) {
-                elem(uv[k].x, zv[k].x, sv[k].x, pv[k].x, qv[k].x);
-                elem(uv[k].y, zv[k].y, sv[k].y, pv[k].y, qv[k].y);
-            }
-        });
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) elem(pu[n - 1], pz[n - 1], pzs[n - 1], pp[n - 1], pq[n - 1]);
-    } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads)
-            elem(pu[i], pz[i], pzs[i], pp[i], pq[i]);
     }
-    block_sum_store<3>(s, partials);
-}
+};
 
 // M <= kPredict predictor vectors per launch: out_k = ((x0 + a_k zeta) + b_k Psi01) + c_k tau in one pass over the inputs
 // (src/NormalForms.jl:410-419, :480, :524).  Psi01 and tau may be NULL: the stream is then not read and its term is dropped.
+// Hand-written on stream_loop, not a pass struct: the optional streams are run-time flags here (as template flags of a struct they
+// make 48 instantiations), and each output is stored as it is formed -- the generic writer, which forms all M outputs of an item
+// before it stores them, measured 1.5 % slower at M = 4 and 2^27 elements.
 constexpr int kPredict = 4;
 struct PredictArgs { double a[kPredict], b[kPredict], c[kPredict]; double* out[kPredict]; };
 
@@ -202,54 +148,18 @@ int v_nf1d_d3(bk_ctx* ctx, size_t n, const double* u, const FoldPoly& Q, const d
 
 // out[3] = (a01, b20, <zeta, zeta*>)
 int v_nf1d_dots(bk_ctx* ctx, size_t n, const double* u, const double* z, const double* zs, const Nf1dPolys& C, double* out) {
-    const bool vec = aligned16(u) && aligned16(z) && aligned16(zs);
-    const bool nth = vec && nt_hint(ctx, n);
-    const int grid = grid_for(n, vec ? 4 : 1, kRedBlocks);        // stream_loop<2>: 2 x 16 B per lane per chunk
-    {
-        ProfScope ps(ctx, "nf1d_dots", 8.0 * n * 3);
-        load_path_dispatch(vec, nth, [&](auto V, auto NT) {
-            hipLaunchKernelGGL((nf1d_dots_kernel<decltype(V)::value, decltype(NT)::value>), dim3(grid), dim3(kThreads), 0,
-                               ctx->stream, n, u, z, zs, C.P, C.Q, ctx->d_partials);
-        });
-        BK_HIP(ctx, hipGetLastError());
-    }
-    BK_TRY(reduce_finish(ctx, grid, 3, 0));
-    for (int k = 0; k < 3; ++k) out[k] = ctx->h_red[k];
-    return 0;
+    return stream_reduce(ctx, "nf1d_dots", n, Nf1dDots{{u, z, zs}, C.P, C.Q}, out);
 }
 
 int v_nf1d_rhs(bk_ctx* ctx, size_t n, const double* u, const double* z, const Nf1dPolys& C, double a01, double b20, double* r1,
                double* r2) {
-    if (n == 0) return 0;
-    const bool vec = aligned16(u) && aligned16(z) && aligned16(r1) && aligned16(r2);
-    const bool nth = vec && nt_hint(ctx, n);
-    const int grid = grid_for(n, vec ? 2 : 1, 4096);
-    ProfScope ps(ctx, "nf1d_rhs", 8.0 * n * 4);
-    load_path_dispatch(vec, nth, [&](auto V, auto NT) {
-        hipLaunchKernelGGL((nf1d_rhs_kernel<decltype(V)::value, decltype(NT)::value>), dim3(grid), dim3(kThreads), 0, ctx->stream,
-                           n, u, z, C.P, C.Q, a01, b20, r1, r2);
-    });
-    BK_HIP(ctx, hipGetLastError());
-    return 0;
+    return stream_write(ctx, "nf1d_rhs", n, Nf1dRhs{{u, z}, {r1, r2}, C.P, C.Q, a01, b20});
 }
 
 // out[3] = (b11, a02, b30)
 int v_nf1d_contract(bk_ctx* ctx, size_t n, const double* u, const double* z, const double* zs, const double* p, const double* q,
                     const Nf1dPolys& C, double* out) {
-    const bool vec = aligned16(u) && aligned16(z) && aligned16(zs) && aligned16(p) && aligned16(q);
-    const bool nth = vec && nt_hint(ctx, n);
-    const int grid = grid_for(n, vec ? 4 : 1, kRedBlocks);
-    {
-        ProfScope ps(ctx, "nf1d_contract", 8.0 * n * 5);
-        load_path_dispatch(vec, nth, [&](auto V, auto NT) {
-            hipLaunchKernelGGL((nf1d_contract_kernel<decltype(V)::value, decltype(NT)::value>), dim3(grid), dim3(kThreads), 0,
-                               ctx->stream, n, u, z, zs, p, q, C.P, C.Q, ctx->d_partials);
-        });
-        BK_HIP(ctx, hipGetLastError());
-    }
-    BK_TRY(reduce_finish(ctx, grid, 3, 0));
-    for (int k = 0; k < 3; ++k) out[k] = ctx->h_red[k];
-    return 0;
+    return stream_reduce(ctx, "nf1d_contract", n, Nf1dContract{{u, z, zs, p, q}, C.P, C.Q}, out);
 }
 
 int v_nf1d_predict(bk_ctx* ctx, size_t n, const double* x0, const double* z, const double* p, const double* t, int m,
@@ -263,18 +173,13 @@ int v_nf1d_predict(bk_ctx* ctx, size_t n, const double* x0, const double* z, con
     const bool nth = vec && nt_hint(ctx, n);
     const int grid = grid_for(n, vec ? 2 : 1, 4096);
     ProfScope ps(ctx, "nf1d_predict", 8.0 * n * (2 + (p ? 1 : 0) + (t ? 1 : 0) + m));
-    auto variant = [&](auto M) {
+    count_dispatch<1, kPredict>(m, [&](auto M) {
         load_path_dispatch(vec, nth, [&](auto V, auto NT) {
             hipLaunchKernelGGL((nf1d_predict_kernel<decltype(M)::value, decltype(V)::value, decltype(NT)::value>), dim3(grid),
                                dim3(kThreads), 0, ctx->stream, n, x0, z, p, t, A);
         });
-    };
-    switch (m) {
-        case 1: variant(std::integral_constant<int, 1>{}); break;
-        case 2: variant(std::integral_constant<int, 2>{}); break;
-        case 3: variant(std::integral_constant<int, 3>{}); break;
-        default: variant(std::integral_constant<int, 4>{}); break;
-    }
+        return 0;
+    });
     BK_HIP(ctx, hipGetLastError());
     return 0;
 }
