@@ -202,6 +202,11 @@ SIGNATURES = {
     "bk_hopf_normal_form": (I, [VP, VP, VP, c_double_p, I, I, D, VP, VP, VP, VP, C.POINTER(GmresOpts), VP, VP, VP, VP, VP,
                                 c_double_p, c_int_p, c_int_p]),
     "bk_hopf_orbit": (I, [VP, SZ, VP, VP, VP, VP, VP, VP, VP, D, D, I, c_double_p, C.POINTER(VP)]),
+    "bk_bautin_rhs3": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP, VP, c_double_p, VP, VP, VP, VP]),
+    "bk_bautin_rhs4": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP, VP, VP, VP, VP, VP, c_double_p, VP, VP, VP]),
+    "bk_bautin_contract": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, c_double_p]),
+    "bk_bautin_normal_form": (I, [VP, VP, VP, c_double_p, I, D, VP, VP, VP, VP, VP, VP, VP, c_double_p, C.POINTER(GmresOpts), VP,
+                                  VP, VP, VP, VP, VP, VP, VP, c_double_p, c_int_p, c_int_p]),
     "bk_d3f": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP]),
     "bk_nf1d_dots": (I, [VP, VP, c_double_p, I, I, VP, VP, c_double_p]),
     "bk_nf1d_rhs": (I, [VP, VP, c_double_p, I, I, VP, D, D, VP, VP]),

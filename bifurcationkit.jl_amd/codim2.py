@@ -1,6 +1,6 @@
 """Fold and Hopf points: refinement and two-parameter continuation with the minimally augmented formulations of
 src/codim2/MinAugFold.jl and MinAugHopf.jl (Hopf: the second half of this module; the Hopf normal form and the periodic-orbit
-predictor of src/NormalForms.jl: its last section), matrix-free on the preconditioned GMRES
+predictor of src/NormalForms.jl and the Bautin normal form of src/codim2/NormalForms.jl: its last sections), matrix-free on the preconditioned GMRES
 path (the reference assembles the systems for MatrixBLS / MinAugMatrixBased, which cannot run at the sizes of this library).
 
   FoldProblem              FoldMinimallyAugmentedFormulation + FoldMAProblem: G(X, p2) = (F(x, p1), sigma(x, p1)), X = (x, p1)
@@ -15,6 +15,10 @@ path (the reference assembles the systems for MatrixBLS / MinAugMatrixBased, whi
 Problems: SwiftHohenberg (2-D / 3-D) and SwiftHohenberg1D -- symmetric, J' = J (:79-84).  sigma_p, dpF and sigma_x are analytic
 (the Jacobians depend on the parameters only through their pointwise term), where the reference takes central differences.
 The bordered vectors v, w of a point are solved once and serve both its residual and its Newton step.
+
+Codim-2 points: on Hopf curves generalised Hopf (Bautin) points are detected, bisected and given their normal form
+(continuation_hopf(..., detect_codim2 = 1 | 2), get_normal_form on a "gh" point); Bogdanov-Takens, zero-Hopf and Hopf-Hopf points
+and the cusp on fold curves are not located (BT, CP and omega are recorded per point, and a Hopf curve stops near omega = 0).
 
 What the two formulations have in common is written once: _MinAugProblem (the cached bordered vectors and the problem surface),
 _MinAugLinearSolver, _continuation_minaug (the PALC loop) and _newton_minaug_mirror (the Newton loop of the mirrors).
@@ -228,12 +232,14 @@ class _MinAugBranch:
 
 def _continuation_minaug(P: _MinAugProblem, lin: _MinAugLinearSolver, what: str, br: _MinAugBranch, guess, p2: float, cp, theta,
                          normC, update_minaug_every_step, save_sol, ds_sequence, verbosity, record_x, skipped, describe,
-                         stop_after=None) -> bool:
+                         stop_after=None, after_record=None) -> bool:
     """PALC on G(X, p2) with a Secant tangent through continuation.newton_palc and BorderingBLS(solver = lin, check_precision =
     false): the two starting points of continuation (Continuation.jl:349-456) by newton on G, step-size control of
     continuation.py or the prescribed ``ds_sequence``.  Every converged point goes into ``br``; its formulation's own fields by
     ``record_x(X, val, tau)`` with val = P.update(...) (a, b renewed) or ``skipped(X)`` when update_minaug_every_step skips it.
-    The run ends when ``stop_after(val)`` holds, and True is returned then."""
+    The run ends when ``stop_after(val)`` holds, and True is returned then.  ``after_record(z, z_old, tau, ds, nopt, bls)``
+    (optional) sees every recorded step of the loop with the state the next step starts from and the step ``ds`` that led from
+    z_old to z (not the one the step-size control chose for the next step); it must leave that state as it is."""
     def record(z, sol, ds_, val, tau):
         record_x(z.u, val, tau)
         br.p2.append(z.p); br.ds.append(ds_)
@@ -278,6 +284,8 @@ def _continuation_minaug(P: _MinAugProblem, lin: _MinAugLinearSolver, what: str,
             tau = Cn.secant_tangent(z, z_old, ds_next, theta)
             val = P.update(z.u, z.p) if Cn.mod_counter(step, update_minaug_every_step) else skipped(z.u)
             record(z, sol, ds, val, tau)
+            if after_record is not None:
+                after_record(z, z_old, tau, ds, nopt, bls)
             if stop_after is not None and stop_after(val):
                 return True
         ds = ds_next
@@ -504,7 +512,8 @@ def continuation_fold(prob, fold_guess: BorderedArray, p2: float, lens2: str, a:
 #   newton_hopf              newton_hopf written out call by call (BorderingBLS.solve_complex, bk_gmres2, hopf_contract)
 #   newton_hopf_native       the same as one library call (bk_newton_hopf)
 #   continuation_hopf        PALC on G(X, p2), Secant tangent, BorderingBLS(HopfLinearSolverMinAug, check_precision = false),
-#                            a / b updated after every step, stop at |omega| < 100 tol (threshBT of update!)
+#                            a / b updated after every step, stop at |omega| < 100 tol (threshBT of update!); detect_codim2 = 1 | 2:
+#                            the first Lyapunov coefficient per point, its sign changes as "gh" points, bisected (_locate_gh)
 #
 # Complex device vectors are (re, im) pairs of HipVecs.  With w^H a = 1:  sigma_x . dx = -w^H d2F[v, dx],
 # sigma_p = -w^H dJ/dp v, sigma_omega = i w^H v.
@@ -751,6 +760,8 @@ class HopfProblem(_MinAugProblem):
 
     _p1 = staticmethod(lambda X: X.p[0])
     _vec = staticmethod(lambda u, s: HopfVec(u, [s.real, s.imag]))
+    keep_vw = False                                 # detection on: update keeps the bordered vectors of the point in last_vw
+    last_vw = None
 
     def _solve_terms(self, X: HopfVec, p2: float):
         return hopf_terms(self.prob, X.u, self.pvec(X.p[0], p2), self.ipar1, X.p[1], self.a, self.b, self.ls)
@@ -765,6 +776,8 @@ class HopfProblem(_MinAugProblem):
         v, w, _ = self.terms(X, p2)
         self.a, self.b = _cscale(w, 1.0 / cnorm(w)), _cscale(v, 1.0 / cnorm(v))
         self._cache = None
+        if self.keep_vw:
+            self.last_vw = (v, w, p2)               # the null vectors of the point: the first Lyapunov coefficient reuses them
         return float(X.p[1])
 
 
@@ -790,32 +803,167 @@ JacobianHopf = _JacobianMinAug
 # ------------------------------------------------------------------------------------------ continuation_hopf
 @dataclass
 class HopfBranch(_MinAugBranch):
-    """The record of continuation_hopf (record_from_solution): p1 (lens1), p2 (lens2), omega and BT = omega per point."""
+    """The record of continuation_hopf (record_from_solution): p1 (lens1), p2 (lens2), omega and BT = omega per point; with
+    detect_codim2 > 0 also l1 (the first Lyapunov coefficient b of the Hopf normal form) and GH = Re b per point, and the
+    generalised Hopf points in ``specialpoint`` (type "gh")."""
     omega: list = field(default_factory=list)
     BT: list = field(default_factory=list)
     stopped_at_bt: bool = False
+    l1: list = field(default_factory=list)
+    GH: list = field(default_factory=list)
+    specialpoint: list = field(default_factory=list)
+    lens2: str | None = None
 
 
 def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls: _GMRES, cp: Cn.ContinuationPar, theta=0.5,
-                      norm_inf=True, update_minaug_every_step=1, save_sol=False, ds_sequence=None, verbosity=0) -> HopfBranch:
+                      norm_inf=True, update_minaug_every_step=1, save_sol=False, ds_sequence=None, verbosity=0,
+                      detect_codim2=0) -> HopfBranch:
     """continuation_hopf(prob, alg = PALC(tangent = Secant()), hopfpointguess, par, lens1, lens2, a, b, options_cont) with
     jacobian_ma = MinAug(): PALC on G(X, p2) through continuation.newton_palc with BorderingBLS(solver = HopfLinearSolverMinAug(),
     check_precision = false), Secant tangent, the two starting points of continuation by newton on G, step-size control of
     continuation.py.  After every converged step a, b are updated (update!) and the run stops once |omega| < 100 tol
     (threshBT: the curve is near a Bogdanov-Takens point).  ``ds_sequence`` (optional) replaces the step-size control by a fixed
-    list of steps.  Codim-2 points are not located."""
-    br = HopfBranch()
+    list of steps.
+
+    ``detect_codim2`` (detect_codim2_bifurcation, MinAugHopf.jl:598-634): 0 locates nothing and issues exactly the library calls
+    of the plain curve.  1: after every converged step the first Lyapunov coefficient of the new point is computed as test_bt_gh
+    does -- zeta = v / |v|, zeta* = w / <zeta, w> from the bordered vectors the step solved, then hopf_normal_form_native -- into
+    br.l1 (b) and br.GH (Re b; the previous value when |Re b| >= 1e5, :632), and every sign change of GH between consecutive
+    points goes to br.specialpoint as type "gh" with the bracketing p2 interval.  2: each sign change is bisected along the curve
+    (_locate_gh) and the special point keeps the located state; the curve continues from the state it had before the bisection,
+    so the recorded points are those of detect_codim2 = 1.  Bogdanov-Takens, zero-Hopf and Hopf-Hopf points are not located."""
+    br = HopfBranch(lens2=lens2)
+    P = HopfProblem(prob, lens2, a, b, ls)
+    P.keep_vw = bool(detect_codim2)
+    if detect_codim2 and update_minaug_every_step != 1:
+        raise ValueError("detect_codim2 needs the bordered vectors of every point (update_minaug_every_step = 1)")
 
     def record_x(X, om, tau):
         br.p1.append(float(X.p[0])); br.omega.append(float(X.p[1])); br.BT.append(om)
+        if detect_codim2:
+            with _solver_state_kept(prob.ctx):
+                l1 = _first_lyapunov(P, X)
+            br.l1.append(l1)
+            br.GH.append(_gh_value(l1, br.GH[-1] if br.GH else math.nan))
 
+    def after_record(z, z_old, tau, ds_taken, nopt, bls):
+        # record() has appended the point: GH[-1] belongs to z, GH[-2] to z_old
+        if len(br.GH) < 2 or not _sign_change(br.GH[-2], br.GH[-1]):
+            return
+        sp = dict(type="gh", idx=len(br.GH) - 1, step=len(br.GH) - 1, p2=float(z.p), interval=tuple(sorted((z_old.p, z.p))),
+                  GH=br.GH[-1], GH_interval=(br.GH[-2], br.GH[-1]), x=z.u.copy(), a=P.a, b=P.b, bisection_steps=0, status="guess")
+        if detect_codim2 > 1:
+            with _solver_state_kept(prob.ctx):
+                sp.update(_locate_gh(P, z, z_old, tau, ds_taken, br.GH[-1], cp, theta, nopt, bls, normC))
+        br.specialpoint.append(sp)
+
+    normC = (lambda z: z.norminf()) if norm_inf else (lambda z: z.norm())
     thresh_bt = 100 * cp.newton_options.tol
     br.stopped_at_bt = _continuation_minaug(
-        HopfProblem(prob, lens2, a, b, ls), HopfLinearSolverMinAug(), "Hopf", br, hopf_guess, p2, cp, theta,
-        (lambda z: z.norminf()) if norm_inf else (lambda z: z.norm()), update_minaug_every_step, save_sol, ds_sequence,
+        P, HopfLinearSolverMinAug(), "Hopf", br, hopf_guess, p2, cp, theta, normC, update_minaug_every_step, save_sol, ds_sequence,
         verbosity, record_x, skipped=lambda X: float(X.p[1]), describe=lambda X: f"p1={X.p[0]:+.8f} omega={X.p[1]:+.8f}",
-        stop_after=lambda om: abs(om) < thresh_bt)
+        stop_after=lambda om: abs(om) < thresh_bt, after_record=after_record if detect_codim2 else None)
     return br
+
+
+# ------------------------------------------------------------------------------------------ generalised Hopf points on the curve
+class _lens2_at:
+    """with _lens2_at(prob, lens2, p2): the problem's parameter ``lens2`` is p2 inside the block (prob._pvec fills the other
+    parameters from prob.params), and what it was afterwards."""
+
+    def __init__(self, prob, lens2, p2):
+        self.prob, self.lens2, self.p2 = prob, lens2, float(p2)
+
+    def __enter__(self):
+        self.old = self.prob.params[self.lens2]
+        self.prob.params[self.lens2] = self.p2
+
+    def __exit__(self, *exc):
+        self.prob.params[self.lens2] = self.old
+        return False
+
+
+class _solver_state_kept:
+    """with _solver_state_kept(ctx): GMRES solves inside the block leave no trace in the state one solve hands to the next on
+    the context (the step count of the last solve, from which the next one sizes its first Arnoldi block, and the carried Newton
+    shifts: the context's "solver_state_hold"), so the solves after the block run exactly as they would have without it."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def __enter__(self):
+        self.ctx.set_option("solver_state_hold", 1)
+
+    def __exit__(self, *exc):
+        self.ctx.set_option("solver_state_hold", 0)
+        return False
+
+
+def _gh_value(l1: complex, previous: float) -> float:
+    """GH of test_bt_gh (MinAugHopf.jl:632): Re l1, or the previous value when |Re l1| >= 1e5."""
+    return float(l1.real) if abs(l1.real) < 1e5 else previous
+
+
+def _sign_change(g0: float, g1: float) -> bool:
+    return g0 * g1 < 0
+
+
+def _first_lyapunov(P: HopfProblem, X: HopfVec, vw=None) -> complex:
+    """b of the Hopf normal form at the point X of the curve from its bordered vectors (test_bt_gh, :598-634): those P.update
+    has just kept, or ``vw`` = (v, w, p2)."""
+    v, w, p2 = vw if vw is not None else P.last_vw
+    zeta = _cscale(v, 1.0 / cnorm(v))
+    zeta_star = _cscale(w, 1.0 / cinner(zeta, w))
+    with _lens2_at(P.prob, P.lens2, p2):
+        return complex(hopf_normal_form_native(P.prob, X, zeta, zeta_star, P.ls).nf.b)
+
+
+def _locate_gh(P: HopfProblem, z, z_old, tau, ds, gh_after: float, cp, theta, nopt, bls, normC) -> dict:
+    """locate_event! (src/events/EventDetection.jl:28-175) for the sign change of GH between z_old and z, on copies of the state:
+    ds, the step that led from z_old to z, is reversed and halved (the first point is the middle of the crossing step), then PALC
+    corrector steps are taken with the step-size control off, ds halved after every step and its sign flipped whenever GH changed sign, until cp.max_bisection_steps, cp.n_inversion, |ds| < cp.dsmin_bisection or an
+    unconverged corrector.  The tangent keeps the orientation of the curve (Secant with the sign of the ds of the step), a and b
+    stay those of the point after the crossing, and the problem's a, b, cache and GMRES count are restored on exit.  Returns the
+    fields of the special point: the last state, its p2 and GH, the bracket, the steps taken and why the bisection ended."""
+    keep = (P.a, P.b, P._cache, P.itlinear, P.last_vw)
+    zc, zp_ = z.copy(), z_old.copy()
+    tau_b = tau.copy()
+    interval = [float(z_old.p), float(z.p)]
+    ind = 1                                          # the end of the bracket the current state replaces
+    sign = gh_after > 0
+    ds_b = -ds / 2.0
+    gh, steps, n_inv, status = gh_after, 0, 0, "max_bisection_steps"
+    try:
+        while steps < cp.max_bisection_steps:
+            if n_inv >= cp.n_inversion:
+                status = "n_inversion"
+                break
+            if abs(ds_b) < cp.dsmin_bisection:
+                status = "dsmin_bisection"
+                break
+            sol = Cn.newton_palc(P, zc, tau_b, zc.copy().add_(tau_b, ds_b), ds_b, theta, bls, nopt, cp.p_min, cp.p_max, normC)
+            if not sol.converged:
+                status = "unconverged"
+                break
+            zp_.copyto_(zc)
+            zc.copyto_(sol.u)
+            steps += 1
+            tau_b = Cn.secant_tangent(zc, zp_, ds_b, theta)
+            v, w, _ = P.terms(zc.u, zc.p)
+            gh = _gh_value(_first_lyapunov(P, zc.u, (v, w, zc.p)), gh)
+            if (gh > 0) == sign:
+                ds_b /= 2.0
+            else:
+                ds_b /= -2.0
+                n_inv += 1
+                ind = 1 - ind
+                sign = gh > 0
+            interval[ind] = float(zc.p)
+    finally:
+        P.a, P.b, P._cache, P.itlinear = keep[:4]
+        P.last_vw = keep[4]
+    return dict(x=zc.u.copy(), p2=float(zc.p), GH=gh, interval=tuple(sorted(interval)), bisection_steps=steps, n_inversion=n_inv,
+                status=status)
 
 
 # ================================================================================================== Hopf normal form
@@ -955,6 +1103,155 @@ def hopf_normal_form_native(prob, X: HopfVec, zeta, zeta_star, ls: _GMRES) -> Ho
                         (it[0], it[1], it[2]), int(ctx.get_option("hopf_nf_unconverged_solves") - bad0))
 
 
+# ------------------------------------------------------------------------------------------ Bautin normal form
+# bautin_normal_form (src/codim2/NormalForms.jl:642-829, detailed = false) for CGL2d, matrix-free, on top of a Hopf record:
+# H11 = Psi110, H20 = 2 Psi200 and G21 = 2 conj(b) come from the Hopf normal form (b = cinner(bv, zeta*) conjugates bv, the
+# reference's G21 = dot(p0, .) conjugates p0).  D = d4F and E = d5F are analytic (the reference nests central differences).
+#
+#   bautin_rhs3, bautin_rhs4, bautin_contract   the device passes (bk_bautin_rhs3, bk_bautin_rhs4, bk_bautin_contract)
+#   bautin_normal_form                          the computation call by call on the plugin surface (ls.solve_complex,
+#                                               BorderingBLS.solve_complex, ls(J, rhs))
+#   bautin_normal_form_native                   the same as one library call (bk_bautin_normal_form)
+@dataclass
+class BautinNormalForm:
+    """The reference's nf = (omega, G21, G32, l2) plus the vectors of the computation (complex ones as (re, im) pairs)."""
+    omega: float | None = None
+    G21: complex | None = None
+    G32: complex | None = None
+    l2: float | None = None
+    H20: object = None
+    H11: object = None
+    H30: object = None
+    H21: object = None
+    H31: object = None
+    H22: object = None
+
+
+@dataclass
+class Bautin:
+    """The reference's Bautin record (x0, params, lens = (lens1, lens2), zeta, zeta_star, nf, type) plus what the four solves
+    reported: ``converged`` (all of them), ``itlinear`` (GMRES counts of the H30, H21, H31, H22 solves) and, from the native call,
+    ``unconverged_solves``."""
+    x0: object
+    params: list
+    lens: tuple
+    zeta: object
+    zeta_star: object
+    nf: BautinNormalForm = field(default_factory=BautinNormalForm)
+    type: str = "?"
+    converged: bool | None = None
+    itlinear: tuple = ()
+    unconverged_solves: int | None = None
+
+
+def bautin_type(l2: float) -> str:
+    """type(::Bautin): the sign of the second Lyapunov coefficient."""
+    return "Subcritical" if l2 > 0 else "Supercritical"
+
+
+def _c2(z):
+    return _ptr(z[0].t), _ptr(z[1].t)
+
+
+def bautin_rhs3(prob, x: HipVec, pars, q, H20, H11: HipVec, G21: complex):
+    """One fused pass (bk_bautin_rhs3): (h30, h21) as (re, im) pairs -- C(q, q, q) + 3 B(q, H20) and
+    G21 q - (C(q, q, conj q) + B(conj q, H20) + 2 B(q, H11))."""
+    ctx = prob.ctx
+    h30, h21 = (x.similar(), x.similar()), (x.similar(), x.similar())
+    g = (C.c_double * 2)(complex(G21).real, complex(G21).imag)
+    ctx.check(ctx.lib.bk_bautin_rhs3(prob.h, _ptr(x.t), _carr(pars), len(pars), *_c2(q), *_c2(H20), _ptr(H11.t), g, *_c2(h30),
+                                     *_c2(h21)), "bk_bautin_rhs3")
+    return h30, h21
+
+
+def bautin_rhs4(prob, x: HipVec, pars, q, H20, H11: HipVec, H30, H21, G21: complex):
+    """One fused pass (bk_bautin_rhs4): (h31 as a (re, im) pair, the real h22), the right-hand sides of the H31 and H22 solves."""
+    ctx = prob.ctx
+    h31, h22 = (x.similar(), x.similar()), x.similar()
+    g = (C.c_double * 2)(complex(G21).real, complex(G21).imag)
+    ctx.check(ctx.lib.bk_bautin_rhs4(prob.h, _ptr(x.t), _carr(pars), len(pars), *_c2(q), *_c2(H20), _ptr(H11.t), *_c2(H30),
+                                     *_c2(H21), g, *_c2(h31), _ptr(h22.t)), "bk_bautin_rhs4")
+    return h31, h22
+
+
+def bautin_contract(prob, x: HipVec, pars, q, p0, H20, H11: HipVec, H30, H21, H31, H22: HipVec) -> complex:
+    """One fused pass over the fifteen vectors (bk_bautin_contract): G32."""
+    ctx = prob.ctx
+    out = (C.c_double * 2)()
+    ctx.check(ctx.lib.bk_bautin_contract(prob.h, _ptr(x.t), _carr(pars), len(pars), *_c2(q), *_c2(p0), *_c2(H20), _ptr(H11.t),
+                                         *_c2(H30), *_c2(H21), *_c2(H31), _ptr(H22.t), out), "bk_bautin_contract")
+    return complex(out[0], out[1])
+
+
+def _bautin_record(hopf: Hopf, lens2, G21, G32, H20, H30, H21, H31, H22, cv, it, bad=None) -> Bautin:
+    l2 = G32.real / 12.0
+    nf = BautinNormalForm(hopf.omega, G21, G32, l2, H20, hopf.nf.Psi110, H30, H21, H31, H22)
+    return Bautin(x0=hopf.x0, params=list(hopf.params), lens=(hopf.lens, lens2), zeta=hopf.zeta, zeta_star=hopf.zeta_star, nf=nf,
+                  type=bautin_type(l2), converged=bool(cv), itlinear=tuple(int(i) for i in it), unconverged_solves=bad)
+
+
+def bautin_normal_form(prob, hopf: Hopf, ls: _GMRES, lens2=None) -> Bautin:
+    """bautin_normal_form (:642-829, detailed = false) call by call on the plugin surface at the Hopf point of the record ``hopf``
+    (hopf_normal_form / hopf_normal_form_native: x0, params, omega, zeta, zeta*, Psi110, Psi200, b): H30 =
+    ls.solve_complex(J, h30, a0 = 3 i omega, a1 = -1), H21 = BorderingBLS(ls, check_precision = false).solve_complex(J, q, p0, 0,
+    h21, 0; shift = -i omega), H31 = ls.solve_complex(J, h31, a0 = 2 i omega, a1 = -1), H22 = -ls(J, h22); the right-hand sides
+    from bautin_rhs3 / bautin_rhs4 and G32 from bautin_contract."""
+    from .hip import HipJacobian
+    x, om, pv = hopf.x0, float(hopf.omega), list(hopf.params)
+    q, p0 = hopf.zeta, hopf.zeta_star
+    nrm = hopf_contract(prob, x, pv, 0, q, p0)[2].conjugate()
+    if not abs(nrm - 1) <= 1e-8:
+        raise ValueError(f"Error of precision in normalization: <zeta, zeta*> = {nrm}, expected 1")
+    H11 = hopf.nf.Psi110
+    H20 = tuple(v.copy().scale_(2.0) for v in hopf.nf.Psi200)
+    G21 = 2.0 * complex(hopf.nf.b).conjugate()
+    J = HipJacobian(prob, x, pv)
+    h30, h21 = bautin_rhs3(prob, x, pv, q, H20, H11, G21)
+    H30, cv30, it30 = ls.solve_complex(J, h30, a0=complex(0.0, 3.0 * om), a1=-1.0)
+    H21, _, cv21, it21 = BorderingBLS(ls, check_precision=False).solve_complex(J, q, p0, 0.0, h21, 0.0, shift=complex(0.0, -om))
+    h31, h22 = bautin_rhs4(prob, x, pv, q, H20, H11, H30, H21, G21)
+    H31, cv31, it31 = ls.solve_complex(J, h31, a0=complex(0.0, 2.0 * om), a1=-1.0)
+    H22, cv22, it22 = ls(J, h22)
+    H22.scale_(-1.0)
+    G32 = bautin_contract(prob, x, pv, q, p0, H20, H11, H30, H21, H31, H22)
+    return _bautin_record(hopf, lens2, G21, G32, H20, H30, H21, H31, H22, cv30 and cv21 and cv31 and cv22,
+                          (it30, int(np.sum(it21)), it31, it22))
+
+
+def bautin_normal_form_native(prob, hopf: Hopf, ls: _GMRES, lens2=None) -> Bautin:
+    """The same as one library call (bk_bautin_normal_form)."""
+    ctx = prob.ctx
+    x, om, pv = hopf.x0, float(hopf.omega), list(hopf.params)
+    H30, H21, H31, H22 = (x.similar(), x.similar()), (x.similar(), x.similar()), (x.similar(), x.similar()), x.similar()
+    b = complex(hopf.nf.b)
+    a = complex(hopf.nf.a) if hopf.nf.a is not None else 0j
+    ab = (C.c_double * 4)(a.real, a.imag, b.real, b.imag)
+    g = (C.c_double * 5)()
+    cv = C.c_int()
+    it = (C.c_int * 4)()
+    lo = ls._opts()
+    bad0 = ctx.get_option("bautin_unconverged_solves")
+    ctx.check(ctx.lib.bk_bautin_normal_form(ctx.h, prob.h, _ptr(x.t), _carr(pv), len(pv), om, *_c2(hopf.zeta), *_c2(hopf.zeta_star),
+                                            _ptr(hopf.nf.Psi110.t), *_c2(hopf.nf.Psi200), ab, C.byref(lo), ls._pl(), *_c2(H30),
+                                            *_c2(H21), *_c2(H31), _ptr(H22.t), g, C.byref(cv), it), "bk_bautin_normal_form")
+    H20 = tuple(v.copy().scale_(2.0) for v in hopf.nf.Psi200)
+    return _bautin_record(hopf, lens2, complex(g[0], g[1]), complex(g[2], g[3]), H20, H30, H21, H31, H22, cv.value,
+                          (it[0], it[1], it[2], it[3]), int(ctx.get_option("bautin_unconverged_solves") - bad0))
+
+
+def _bautin_from_branch(br, ind: int, prob, ls: _GMRES, tol, max_iterations, norm_inf) -> Bautin:
+    """A "gh" point of a HopfBranch: newton_hopf_native at the located p2 from the located state -> hopf_eigenpair ->
+    hopf_normal_form_native -> bautin_normal_form_native (the normal form at the REFINED Hopf point of the located p2)."""
+    sp = br.specialpoint[ind]
+    with _lens2_at(prob, br.lens2, sp["p2"]):
+        s = newton_hopf_native(prob, sp["x"], sp["a"], sp["b"], ls, tol=tol, max_iterations=max_iterations, norm_inf=norm_inf)
+        if not s["converged"]:
+            raise RuntimeError(f"get_normal_form: newton_hopf did not converge from the located point (residuals {s['residuals']})")
+        zeta, zeta_star = hopf_eigenpair(prob, s)
+        hp = hopf_normal_form_native(prob, s["u"], zeta, zeta_star, ls)
+        return bautin_normal_form_native(prob, hp, ls, lens2=br.lens2)
+
+
 def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, max_iterations=15, norm_inf=False, seed=0,
                     bls=None, refine=True):
     """get_normal_form(br, ind) (src/NormalForms.jl:1102-1204) for a point of type "hopf" of a branch of
@@ -962,10 +1259,14 @@ def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, 
     random start, or start_with_eigen when ``eig`` is given) -> newton_hopf_native -> hopf_eigenpair -> hopf_normal_form_native.
     The normal form is taken at the REFINED point (the reference takes the bisected one).  For a Swift-Hohenberg problem a point of
     type "bp" or "fold" goes to normal_form1d.get_normal_form1d (``bls``, ``refine`` as there) and returns its SimpleBranchPoint;
-    "nd" points, and "bp" / "fold" points of any other problem, have no normal form here."""
+    "nd" points, and "bp" / "fold" points of any other problem, have no normal form here.  A point of type "gh" of a HopfBranch
+    (continuation_hopf(..., detect_codim2 > 0)) returns its Bautin record: newton_hopf_native at the located p2 ->
+    hopf_eigenpair -> hopf_normal_form_native -> bautin_normal_form_native."""
     from . import normal_form1d as N1
     sh = N1.is_sh_problem(prob)                     # decided before the branch is looked at
     kind = br.specialpoint[ind].get("type")
+    if kind == "gh" and isinstance(br, HopfBranch):
+        return _bautin_from_branch(br, ind, prob, ls, tol, max_iterations, norm_inf)
     if sh and kind in ("bp", "fold"):
         return N1.get_normal_form1d(br, ind, prob, ls, bls=bls, eig=eig, nev=nev, refine=refine, tol=tol,
                                     max_iterations=max_iterations, norm_inf=norm_inf)

@@ -102,6 +102,7 @@ struct bk_ctx {
         double fold_unconverged = 0.0;                                             // bk_newton_fold: bordered-vector / step solves that returned unconverged
         double hopf_unconverged = 0.0;                                             // bk_newton_hopf: the same count for the Hopf system
         double hopf_nf_unconverged = 0.0;                                          // bk_hopf_normal_form: solves (of three per call) that returned unconverged
+        double bautin_unconverged = 0.0;                                           // bk_bautin_normal_form: solves (of four per call) that returned unconverged
         double nf1d_unconverged = 0.0;                                             // bk_normal_form_1d: solves (three with bordering, two matrix-free) that returned unconverged
     } diag;
     double* diag_slot(const std::string& key) {
@@ -114,11 +115,15 @@ struct bk_ctx {
         if (key == "fold_unconverged_solves") return &diag.fold_unconverged;
         if (key == "hopf_unconverged_solves") return &diag.hopf_unconverged;
         if (key == "hopf_nf_unconverged_solves") return &diag.hopf_nf_unconverged;
+        if (key == "bautin_unconverged_solves") return &diag.bautin_unconverged;
         if (key == "nf1d_unconverged_solves") return &diag.nf1d_unconverged;
         return nullptr;
     }
     std::vector<double> newton_shifts; // option gmres_newton_carry: Leja-ordered Ritz values of the last GMRES solve (solver.hip)
     int gmres_last_steps = 1 << 20;   // Arnoldi steps of the previous GMRES solve (speculation ramp of the device-resident chunks)
+    bool solver_state_held = false;   // "solver_state_hold" (bk_ctx_set_option): the two fields above as they were when it was set to 1
+    int held_steps = 0;
+    std::vector<double> held_shifts;
     const double* eig_x0 = nullptr;   // one-shot start vector of the next eigensolve (bk_eig_set_start_vector)
     // second execution lane (context.hip: ctx_lane): an independent context on the same device -- own non-blocking stream,
     // reduction buffers, workspace pool, profile -- on which the second of two independent linear solves runs concurrently

@@ -742,6 +742,17 @@ int bk_ctx_set_lane_comm(bk_ctx* ctx, bk_allreduce_fn allreduce, bk_sendrecv_fn 
 int bk_ctx_set_option(bk_ctx* ctx, const char* key, double value) {
     if (!ctx || !key) return -1;
     if (double* d = ctx->diag_slot(key)) { *d = value; return 0; }
+    // not an option (bkhip.h): 1 puts aside what the next GMRES solve takes over from the previous one -- the step count that sizes
+    // its first block and the carried Newton shifts, the state linsolve2 keeps between its two solves -- and 0 puts it back.  No
+    // buffer depends on it, so the lanes stay warm.
+    if (std::string(key) == "solver_state_hold") {
+        if (value != 0.0) {
+            ctx->held_steps = ctx->gmres_last_steps; ctx->held_shifts = ctx->newton_shifts; ctx->solver_state_held = true;
+        } else if (ctx->solver_state_held) {
+            ctx->gmres_last_steps = ctx->held_steps; ctx->newton_shifts = ctx->held_shifts; ctx->solver_state_held = false;
+        }
+        return 0;
+    }
     ctx->opts[key] = value;
     ctx->lanes_warm.clear();                 // (another option set may ask the pools for other buffers: linsolve2 warms them again)
     return 0;
@@ -750,6 +761,7 @@ int bk_ctx_set_option(bk_ctx* ctx, const char* key, double value) {
 int bk_ctx_get_option(bk_ctx* ctx, const char* key, double* value) {
     if (!ctx || !key || !value) return -1;
     if (const double* d = ctx->diag_slot(key)) { *value = *d; return 0; }
+    if (std::string(key) == "solver_state_hold") { *value = ctx->solver_state_held ? 1.0 : 0.0; return 0; }
     auto it = ctx->opts.find(key);
     if (it == ctx->opts.end()) return set_error(ctx, "unknown option %s", key);
     *value = it->second;

@@ -1,8 +1,9 @@
-// The pointwise tensors of the cGL nonlinearity (examples/cGL2d.jl:24-40) that the Hopf formulation (hopf.hip) and the Hopf
-// normal form (hopf_nf.hip) contract:
+// The pointwise tensors of the cGL nonlinearity (examples/cGL2d.jl:24-40) that the Hopf formulation (hopf.hip), the Hopf
+// normal form (hopf_nf.hip) and the Bautin normal form (bautin.hip) contract:
 //   NL(z) = (r + i nu) z - (c3 + i mu) |z|^2 z - c5 |z|^4 z + gamma,   z = u1 + i u2,
 // per grid point and field f: the Hessian H_f (symmetric 2 x 2), the third derivative T_f (symmetric 2 x 2 x 2) and
-// dJ/dp = D_p (2 x 2), all in closed form.  The Laplacian is linear, so d2F = d2NL and d3F = d3NL.
+// dJ/dp = D_p (2 x 2), all in closed form, and for the Bautin normal form the fourth and fifth derivatives with the helpers that
+// contract a symmetric tensor with complex 2-vectors.  The Laplacian is linear, so dkF = dkNL for k >= 2.
 // Internal header.
 #pragma once
 #include "common.h"
@@ -39,6 +40,71 @@ __device__ __forceinline__ void cgl_d3(const CglCoef& c, double u1, double u2, d
     t[5] = -2.0 * c.c3 - c.c5 * s;
     t[6] = -2.0 * c.mu - c.c5 * m;
     t[7] = -6.0 * c.c3 - c.c5 * (12.0 * a + 60.0 * b);
+}
+
+// Fourth derivative of NL at (u1, u2), the u-derivative of cgl_d3: only the quintic term contributes and it is linear in u.  Per
+// field the five independent entries of the symmetric tensor in the order (1111, 1112, 1122, 1222, 2222), field 1 in d[0..4],
+// field 2 in d[5..9].
+__device__ __forceinline__ void cgl_d4(const CglCoef& c, double u1, double u2, double d[10]) {
+    const double a = -24.0 * c.c5, p = a * u1, q = a * u2;
+    d[0] = 5.0 * p; d[1] = q; d[2] = p; d[3] = q; d[4] = p;
+    d[5] = q; d[6] = p; d[7] = q; d[8] = p; d[9] = 5.0 * q;
+}
+
+// Fifth derivative of NL, the u-derivative of cgl_d4: constant.  Per field the six entries (11111, 11112, 11122, 11222, 12222,
+// 22222), field 1 in e[0..5], field 2 in e[6..11].
+__device__ __forceinline__ void cgl_d5(const CglCoef& c, double e[12]) {
+    const double a = -24.0 * c.c5;
+    e[0] = 5.0 * a; e[1] = 0.0; e[2] = a; e[3] = 0.0; e[4] = a; e[5] = 0.0;
+    e[6] = 0.0; e[7] = a; e[8] = 0.0; e[9] = a; e[10] = 0.0; e[11] = 5.0 * a;
+}
+
+// ---- complex arguments: a complex number, a complex 2-vector (one per field) and the contraction of a symmetric tensor of the
+// two fields with it.  A symmetric tensor of order K is held as its K + 1 entries t[j], j = how many of its indices are 2; one
+// argument v lowers the order by one, o[j] = t[j] v.a + t[j + 1] v.b, and K arguments leave the scalar o[0].
+struct Cx { double r, i; };
+struct Cx2 { Cx a, b; };
+struct Re2 { double a, b; };
+__device__ __forceinline__ Cx cx(double r, double i = 0.0) { return Cx{r, i}; }
+__device__ __forceinline__ Cx operator+(Cx x, Cx y) { return Cx{x.r + y.r, x.i + y.i}; }
+__device__ __forceinline__ Cx operator-(Cx x, Cx y) { return Cx{x.r - y.r, x.i - y.i}; }
+__device__ __forceinline__ Cx operator*(Cx x, Cx y) { return Cx{x.r * y.r - x.i * y.i, x.r * y.i + x.i * y.r}; }
+__device__ __forceinline__ Cx operator*(double s, Cx y) { return Cx{s * y.r, s * y.i}; }
+__device__ __forceinline__ Cx conj(Cx x) { return Cx{x.r, -x.i}; }
+__device__ __forceinline__ Cx2 conj(Cx2 v) { return Cx2{conj(v.a), conj(v.b)}; }
+__device__ __forceinline__ Cx2 operator*(double s, Cx2 v) { return Cx2{s * v.a, s * v.b}; }
+__device__ __forceinline__ Cx2 operator+(Cx2 v, Cx2 w) { return Cx2{v.a + w.a, v.b + w.b}; }
+
+template <int K>
+__device__ __forceinline__ void sym_lower(const double (&t)[K + 1], Cx2 v, Cx (&o)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) o[j] = t[j] * v.a + t[j + 1] * v.b;
+}
+template <int K>
+__device__ __forceinline__ void sym_lower(const Cx (&t)[K + 1], Cx2 v, Cx (&o)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) o[j] = t[j] * v.a + t[j + 1] * v.b;
+}
+template <int K>
+__device__ __forceinline__ void sym_lower(const double (&t)[K + 1], Re2 v, double (&o)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) o[j] = t[j] * v.a + t[j + 1] * v.b;
+}
+template <int K>
+__device__ __forceinline__ void sym_conj(const Cx (&t)[K], Cx (&o)[K]) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) o[j] = conj(t[j]);
+}
+// the last argument: a tensor of order 1 against v
+__device__ __forceinline__ Cx sym_dot(const Cx (&t)[2], Cx2 v) { return t[0] * v.a + t[1] * v.b; }
+__device__ __forceinline__ Cx sym_dot(const Cx (&t)[2], Re2 v) { return v.a * t[0] + v.b * t[1]; }
+__device__ __forceinline__ Cx sym_dot(const double (&t)[2], Cx2 v) { return t[0] * v.a + t[1] * v.b; }
+__device__ __forceinline__ double sym_dot(const double (&t)[2], Re2 v) { return t[0] * v.a + t[1] * v.b; }
+// a tensor of order 2 against (v, w)
+__device__ __forceinline__ Cx sym_dot(const Cx (&t)[3], Cx2 v, Cx2 w) {
+    Cx o[2];
+    sym_lower<2>(t, v, o);
+    return sym_dot(o, w);
 }
 
 // dJ/dp at (u1, u2) for params[ipar] = (r, mu, nu, c3, c5, gamma): D = [[d[0], d[1]], [d[2], d[3]]]

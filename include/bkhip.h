@@ -85,7 +85,12 @@ int bk_ctx_destroy(bk_ctx* ctx);
 const char* bk_last_error(bk_ctx* ctx);
 int bk_ctx_sync(bk_ctx* ctx);
 /* Tuning knobs ("sh_kernel": 0 gather / 1 streaming; "sh_zchunk"; "dgks_eta"; "dct_fft"; "dct_roundtrip";
- * "dct_gemm"; "halo_overlap"; ...): experiments and cross-checks, the defaults are the measured optimum.        */
+ * "dct_gemm"; "halo_overlap"; ...): experiments and cross-checks, the defaults are the measured optimum.
+ * One key is no knob: "solver_state_hold".  Set to 1 it puts aside the state a GMRES solve hands to the next one on this
+ * context (the Arnoldi step count of the last solve, from which the next sizes its first block, and with "gmres_newton_carry"
+ * the carried shifts); set to 0 it puts that state back.  Solves made in between leave no trace, so the solves after them run
+ * exactly as they would have without them (continuation_hopf's codim-2 detection between curve steps).  One level: a second 1
+ * before the 0 overwrites what is held; 0 with nothing held does nothing.  Reading it gives 1 while a state is held.  */
 int bk_ctx_set_option(bk_ctx* ctx, const char* key, double value);
 int bk_ctx_get_option(bk_ctx* ctx, const char* key, double* value);
 /* Per-kernel timing with HIP events on the context's stream (bench.py's roofline leg):
@@ -595,6 +600,54 @@ int bk_hopf_normal_form(bk_ctx* ctx, bk_problem* prob, const double* x, const do
 int bk_hopf_orbit(bk_ctx* ctx, size_t n, const double* x0, const double* z_re, const double* z_im, const double* psi001,
                   const double* psi110, const double* psi200_re, const double* psi200_im, double ds, double amp, int M,
                   const double* t, double* const* out);
+
+/* ------------------------------------------------------------------ Bautin normal form -------------------
+ * bautin_normal_form (src/codim2/NormalForms.jl:642-829, detailed = false), matrix-free, for BK_PDE_CGL2D (any other problem:
+ * the error of the Hopf entries above).  At a Hopf point (x, params, omega) with q = zeta, p0 = zeta*, <zeta, zeta*> = 1,
+ * dot(p0, h) = sum conj(p0) h and B, C, D, E the 2nd .. 5th derivatives of the right-hand side at x:
+ *   H20 = (2 i omega - J) \ B(q, q) = 2 Psi200,  H11 = -J \ B(q, conj q) = Psi110,  G21 = 2 conj(b)   (bk_hopf_normal_form)
+ *   H30 = (3 i omega - J) \ (C(q, q, q) + 3 B(q, H20))
+ *   H21 : [J - i omega, q; p0^H, 0][H21; s] = [G21 q - (C(q, q, conj q) + B(conj q, H20) + 2 B(q, H11)); 0]
+ *   H31 = (2 i omega - J) \ (D(q, q, q, conj q) + 3 C(q, q, H11) + 3 C(q, conj q, H20) + 3 B(H20, H11) + B(conj q, H30)
+ *                            + 3 B(q, H21) - 3 G21 H20)
+ *   H22 = -J \ (D(q, q, conj q, conj q) + 4 C(q, conj q, H11) + C(conj q, conj q, H20) + C(q, q, conj H20) + 2 B(H11, H11)
+ *               + 2 B(q, conj H21) + 2 B(conj q, H21) + B(conj H20, H20) - 4 Re(G21) H11)               (real)
+ *   G32 = dot(p0, E(q, q, q, conj q, conj q) + D(q, q, q, conj H20) + 3 D(q, conj q, conj q, H20) + 6 D(q, q, conj q, H11)
+ *                 + C(conj q, conj q, H30) + 3 C(q, q, conj H21) + 6 C(q, conj q, H21) + 3 C(q, conj H20, H20)
+ *                 + 6 C(q, H11, H11) + 6 C(conj q, H20, H11) + 2 B(conj q, H31) + 3 B(q, H22) + B(conj H20, H30)
+ *                 + 3 B(conj H21, H20) + 6 B(H11, H21)),        l2 = Re G32 / 12  (the second Lyapunov coefficient).
+ * D and E are analytic (only the quintic term of cGL contributes) where the reference nests central differences of d3F
+ * (:757-794).  Complex vectors are (re, im) pairs; H11 and H22 are real.                                                   */
+/* One pass over u, q, H20, H11: (h30_re, h30_im) = C(q, q, q) + 3 B(q, H20) and (h21_re, h21_im) = G21 q - (C(q, q, conj q) +
+ * B(conj q, H20) + 2 B(q, H11)) with the host scalar g21 = (Re G21, Im G21).  The outputs are distinct and alias no input.  */
+int bk_bautin_rhs3(bk_problem* prob, const double* u, const double* params, int nparams, const double* q_re, const double* q_im,
+                   const double* h20_re, const double* h20_im, const double* h11, const double g21[2], double* h30_re,
+                   double* h30_im, double* h21_re, double* h21_im);
+/* One pass over u, q, H20, H11, H30, H21: (h31_re, h31_im) and the real h22, the right-hand sides of the H31 and H22 solves
+ * above (h22 before the sign: H22 = -J \ h22).  The outputs are distinct and alias no input.                              */
+int bk_bautin_rhs4(bk_problem* prob, const double* u, const double* params, int nparams, const double* q_re, const double* q_im,
+                   const double* h20_re, const double* h20_im, const double* h11, const double* h30_re, const double* h30_im,
+                   const double* h21_re, const double* h21_im, const double g21[2], double* h31_re, double* h31_im, double* h22);
+/* One streaming pass over the fifteen vectors u, q, p0, H20, H11, H30, H21, H31, H22: host out[2] = (Re G32, Im G32).
+ * Deterministic, all-reduced.                                                                                             */
+int bk_bautin_contract(bk_problem* prob, const double* u, const double* params, int nparams, const double* q_re, const double* q_im,
+                       const double* p_re, const double* p_im, const double* h20_re, const double* h20_im, const double* h11,
+                       const double* h30_re, const double* h30_im, const double* h21_re, const double* h21_im,
+                       const double* h31_re, const double* h31_im, const double* h22, double out[2]);
+/* The whole computation at (x, params, omega) from the outputs of bk_hopf_normal_form at the same point (psi110, psi200 and
+ * ab[4] = (Re a, Im a, Re b, Im b); none is modified): the pass of bk_bautin_rhs3, H30 by bk_gmres_cshift (a0 = 3 i omega,
+ * a1 = -1), H21 by bk_bls_bordering_cshift(J, q, p0, 0, h21, 0; shift = -i omega), the pass of bk_bautin_rhs4, H31 by
+ * bk_gmres_cshift (a0 = 2 i omega, a1 = -1), H22 by the real solve, negated, and the pass of bk_bautin_contract.
+ * g[5] = (Re G21, Im G21, Re G32, Im G32, l2).  The four H vectors (seven real arrays) are outputs, distinct from each other and from the inputs.
+ * zeta and zeta* come normalised; unless |<zeta, zeta*> - 1| <= 1e-8 the call is an error.  *converged = all four solves
+ * converged; itlinear[4] = GMRES counts of the H30, H21 (both solves of the bordering), H31 and H22 solves.  J - i omega is
+ * singular at a Hopf point by construction, so an unconverged solve is no error: each adds 1 to the context counter
+ * "bautin_unconverged_solves".                                                                                            */
+int bk_bautin_normal_form(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, double omega,
+                          const double* z_re, const double* z_im, const double* zs_re, const double* zs_im, const double* psi110,
+                          const double* psi200_re, const double* psi200_im, const double ab[4], const bk_gmres_opts* lsopts,
+                          bk_precond* pl, double* h30_re, double* h30_im, double* h21_re, double* h21_im, double* h31_re,
+                          double* h31_im, double* h22, double g[5], int* converged, int itlinear[4]);
 
 /* ------------------------------------------------------------------ normal form, 1-D kernel -------------
  * get_normal_form1d (src/NormalForms.jl:189-353) and the vectors of its predictors (:389-531), matrix-free, for BK_PDE_SH
