@@ -145,6 +145,7 @@ SIGNATURES = {
     "bk_precond_destroy": (I, [VP]),
     "bk_precond_apply": (I, [VP, VP, VP]),
     "bk_precond_op_apply": (I, [VP, VP, VP, VP, D, D, VP, c_int_p]),
+    "bk_precond_check_norm": (I, [VP, VP, VP, VP, VP, D, D, I, c_double_p, c_int_p]),
     "bk_gmres_default_opts": (None, [C.POINTER(GmresOpts), I]),
     "bk_gmres": (I, [VP, VP, VP, VP, D, D, C.POINTER(GmresOpts), VP, c_int_p, c_int_p, c_double_p]),
     "bk_gmres2": (I, [VP, VP, VP, VP, VP, VP, D, D, C.POINTER(GmresOpts), VP, c_int_p, c_int_p]),

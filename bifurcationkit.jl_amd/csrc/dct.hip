@@ -881,6 +881,50 @@ struct ShDctPrecond : bk_precond {
         *dot = ctx->h_red[0];
         return 0;
     }
+    // |Pl \ v| from the spectrum: forward on every axis but the last, then the norm-only round trip on the last one (dct_fast.hip: NRM)
+    // -- the conditions of apply_dot, the round trip on, and that pass on the fused kernel's tiling (it reads the plan's own scratch)
+    bool nrm2_spectral_ok() const override {
+        if (!plan || plan->kind >= 1 || plan->dist || plan->slab_ok || plan->ndim < 2 || ctx->nranks != 1) return false;
+        if (ctx->opt("dct_fft", 1.0) == 0.0 || ctx->opt("dct_roundtrip", 1.0) == 0.0 || !plan->t1 || !plan->t2) return false;
+        for (int a = 0; a < plan->ndim; ++a)
+            if (!plan->twid[a]) return false;
+        const int last = plan->ndim - 1;
+        return dct_axis_nrm_ok(ctx, plan->n[0], plan->n[1], plan->n[2], last, last == 1 ? plan->t1 : plan->t2);
+    }
+    int apply_nrm2(const double* v, double c, const double* add, double* nrm2_out) override {
+        if (!nrm2_spectral_ok()) return bk_precond::apply_nrm2(v, c, add, nrm2_out);
+        const int n0 = plan->n[0], n1 = plan->n[1], n2 = plan->n[2], last = plan->ndim - 1;
+        auto pass = [&](int a, const double* in, double* o, int fuse, int* nb, double bytes, const DctFuse* f) -> int {
+            ProfScope ps(ctx, "dct_pass", bytes * plan->total);
+            return dct_axis_fft(ctx, n0, n1, n2, a, 0, plan->twid[a], in, o, plan->lam[0], plan->lam[1],
+                                plan->ndim == 3 ? plan->lam[2] : nullptr, plan->shift, fuse, nullptr, nb, f);
+        };
+        const double* src = v;
+        double* bufs[2] = {plan->t1, plan->t2};
+        DctFuse f;
+        const DctFuse* f0 = nullptr;
+        if (add) {
+            // v + c add rides in the x-forward pass where that is the fused kernel (FZS: the sum is formed per sample and also stored --
+            // into t2, which nothing reads before the next pass overwrites it); else one axpbyz pass into t2 first
+            if (ctx->opt("dct_fuse_pw", 1.0) != 0.0 && ((((uintptr_t)v) | ((uintptr_t)add)) & 15) == 0 &&
+                dct_axis_fused_ok(ctx, n0, n1, n2, 0, v, plan->t1, 0)) {
+                f.add = add; f.cadd = c; f.store = plan->t2;
+                f0 = &f;
+            } else {
+                BK_TRY(v_axpbyz(ctx, n, 1.0, v, c, add, plan->t2));
+                src = plan->t2;
+            }
+        }
+        for (int a = 0; a < last; ++a) {
+            BK_TRY(pass(a, src, bufs[a], 0, nullptr, (a == 0 && f0) ? 32.0 : 16.0, a == 0 ? f0 : nullptr));
+            src = bufs[a];
+        }
+        int nb = 0;
+        BK_TRY(pass(last, src, nullptr, 3, &nb, 8.0, nullptr));
+        BK_TRY(reduce_finish(ctx, nb, 1, 0));
+        *nrm2_out = sqrt(ctx->h_red[0]);
+        return 0;
+    }
     int apply_dot(const double* v, double* out, double* dot) override {
         if (plan->kind >= 1 || plan->dist || plan->ndim < 2 || ctx->nranks != 1) return bk_precond::apply_dot(v, out, dot);
         int nb = 0;

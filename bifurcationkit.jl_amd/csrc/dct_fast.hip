@@ -397,8 +397,12 @@ __device__ __forceinline__ c2 lane_xor1(c2 v) { c2 r; r.x = lane_xor1(v.x); r.y 
 // today's code generation, checked on the device by tests/test_gpu_dct_const_len.py, not guaranteed by construction.  (The x passes
 // at N = 512 did come out different in the last bit, and the y passes ran slower; both stay at the runtime length --
 // profiles/r8_const_len_isa.txt.)
+// NRM (with MODE 2, runtime length): the norm-only round trip of a solve's explicit residual check (dct.hip: ShDctPrecond::apply_nrm2).
+// The tile runs the first stage, the forward middle stages and the merged middle's forward half, and sums sym_k^2 |v^_k|^2 -- by
+// Parseval |M^-1 v|^2 of this tile's lines -- into P.dotp[workgroup] exactly as DOT sums sym_k |v^_k|^2: same symbol, same rcp_nr,
+// fixed summation order, no atomics.  No inverse stages, no last stage, no global store: 8 B/point.
 template <int NT, int MODE, bool AX0, bool NTM, bool DOT = false, bool FZ = false, int SLAB = 0, bool FZS = false, bool TURN = false,
-          int CN = 0>   // MODE 0: forward, 1: inverse, 2: forward - symbol - inverse (AX0: 0 / 1 only)
+          int CN = 0, bool NRM = false>   // MODE 0: forward, 1: inverse, 2: forward - symbol - inverse (AX0: 0 / 1 only)
 __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P) {
     constexpr bool SPLIT = NT == 512;
     static_assert(!TURN || (MODE == 1 && AX0 && !DOT && SLAB == 0 && !FZS && !SPLIT), "TURN: the x inverse pass only");
@@ -407,6 +411,7 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
     static_assert(!FZ || (AX0 && MODE != 2), "FZ: x passes only");
     static_assert(SLAB == 0 || (!AX0 && !FZ && !DOT && ((SLAB == 1 && MODE == 0) || (SLAB == 2 && MODE == 1))), "SLAB: z halves only");
     static_assert(CN == 0 || (CN == 512 && NT == 256 && MODE == 2 && !AX0), "compile-time length: the 256-lane z round trip at N = 512");
+    static_assert(!NRM || (MODE == 2 && !AX0 && NT == 256 && !DOT && SLAB == 0 && CN == 0), "NRM: the 256-lane round trip at the runtime length");
     constexpr int CBITS = CN == 512 ? 9 : 0;
     constexpr int CAX = CN == 0 ? -1 : 2;
     __shared__ double dsum[NT / 64];
@@ -757,6 +762,14 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                     const double sa = CAX == 2 ? ca + lk : ca + lk + lo2, sb = CAX == 2 ? cb + lk : cb + lk + lo2;
                     c2 r; r.x = rcp_nr(sa * sa + P.shift, 2); r.y = rcp_nr(sb * sb + P.shift, 2); return r;
                 };
+                if (NRM) {
+                    // the forward half alone (MODE 0 hands over the orthonormal coefficient v^_k of lines a / b): (sym_k v^_k)^2 summed
+                    dctc::fused_mid<0, false>(zp, N, t, tw, ew, s0, s2, nold, [&](int k, c2 v) {
+                        const c2 f = sym(k);
+                        const double ya = v.x * f.x, yb = v.y * f.y;
+                        dtot.x = fma(ya, ya, dtot.x); dtot.y = fma(yb, yb, dtot.y);
+                    }, nosym, dtot);
+                } else
                 dctc::fused_mid<2, DOT>(zp, N, t, tw, ew, s0, s2, nold, nost, sym, dtot);
             } else if (MODE == 0 && SLAB == 1) {
                 dctc::fused_mid<0, false>(zp, N, t, tw, ew, s0, s2, nold, [&](int k, c2 v) {
@@ -810,18 +823,22 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
             if (P.trace) { __builtin_amdgcn_s_waitcnt(0); stamp(6); }
             return;
         }
-        if (MODE == 2 && DOT) {
+        if (MODE == 2 && (DOT || NRM)) {
             double d = dtot.x + dtot.y;
             for (int off = 32; off > 0; off >>= 1) d += __shfl_down(d, off, 64);
             if ((tid & 63) == 0) dsum[tid >> 6] = d;
         }
         lds_barrier();
-        if (MODE == 2 && DOT && tid == 0) {
+        if (MODE == 2 && (DOT || NRM) && tid == 0) {
             double d = dsum[0];
             for (int w = 1; w < NT / 64; ++w) d += dsum[w];
             P.dotp[blockIdx.x] = d;
         }
         stamp(4);
+        if (NRM) {                                                 // the sum is all this pass leaves behind
+            if (P.trace) { __builtin_amdgcn_s_waitcnt(0); stamp(6); }
+            return;
+        }
         for (int top = bits - 3; top > 3;) {
             const int R = top - 3 >= 3 ? 3 : top - 3;
             middle(top - R, R, true);
@@ -909,11 +926,11 @@ inline int choose_lt(int N, int axis, int n0, size_t rows, bool wide = false) {
 
 // The 256-lane fused passes: x forward / inverse (plain, FZ, FZS, TURN shifted / unshifted), y forward / inverse and the z round trip
 // with and without DOT at the runtime length (CN = 0); the z round trip also at the compile-time length (CN = 512) -- NTM on and off.
-// The slab halves and the 512-lane round trip are launched by the caller.
-template <int MODE, bool AX0, bool DOT, bool FZ, bool FZS, bool TURN, int CN>
+// The norm-only round trip (NRM) at the runtime length only.  The slab halves and the 512-lane round trip are launched by the caller.
+template <int MODE, bool AX0, bool DOT, bool FZ, bool FZS, bool TURN, int CN, bool NRM = false>
 void launch_fused_ntm(const FftK& P, unsigned grid, size_t lds, hipStream_t st, bool ntm) {
-    if (ntm) hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, true, DOT, FZ, 0, FZS, TURN, CN>), dim3(grid), dim3(256), lds, st, P);
-    else hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, false, DOT, FZ, 0, FZS, TURN, CN>), dim3(grid), dim3(256), lds, st, P);
+    if (ntm) hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, true, DOT, FZ, 0, FZS, TURN, CN, NRM>), dim3(grid), dim3(256), lds, st, P);
+    else hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, false, DOT, FZ, 0, FZS, TURN, CN, NRM>), dim3(grid), dim3(256), lds, st, P);
 }
 
 void launch_fused_x(const FftK& P, unsigned grid, size_t lds, hipStream_t st, int mode, bool ntm, bool turn, bool fz, bool fzs) {
@@ -927,8 +944,9 @@ void launch_fused_x(const FftK& P, unsigned grid, size_t lds, hipStream_t st, in
     else launch_fused_ntm<0, true, false, false, false, false, 0>(P, grid, lds, st, ntm);
 }
 
-void launch_fused_yz(const FftK& P, unsigned grid, size_t lds, hipStream_t st, int mode, bool ntm, bool dot, bool const_len) {
-    if (mode == 2 && const_len) {
+void launch_fused_yz(const FftK& P, unsigned grid, size_t lds, hipStream_t st, int mode, bool ntm, bool dot, bool const_len, bool nrm) {
+    if (nrm) launch_fused_ntm<2, false, false, false, false, false, 0, true>(P, grid, lds, st, ntm);
+    else if (mode == 2 && const_len) {
         if (dot) launch_fused_ntm<2, false, true, false, false, false, 512>(P, grid, lds, st, ntm);
         else launch_fused_ntm<2, false, false, false, false, false, 512>(P, grid, lds, st, ntm);
     } else if (mode == 2 && dot) launch_fused_ntm<2, false, true, false, false, false, 0>(P, grid, lds, st, ntm);
@@ -960,6 +978,22 @@ bool dct_axis_fused_ok(bk_ctx* ctx, int n0, int n1, int n2, int axis, const doub
     return n0 % LT == 0;
 }
 
+// lines per tile of an axis >= 1 pass as dct_axis_fft chooses them (option dct_lt: the experiment knob)
+static int fused_lt(bk_ctx* ctx, int N, int axis, int n0, size_t rows, bool fused_ok) {
+    int LT = choose_lt(N, axis, n0, rows, fused_ok && ctx->opt("dct_lt_wide", 1.0) != 0.0);
+    const int lt_opt = (int)ctx->opt("dct_lt", 0.0);
+    if (lt_opt >= 2 && axis != 0 && lt_opt <= LT) LT = lt_opt & ~1;
+    return LT;
+}
+
+// the norm-only round trip (fuse_scale 3) of this axis runs: the fused kernel's tiling and one partial sum per tile
+bool dct_axis_nrm_ok(bk_ctx* ctx, int n0, int n1, int n2, int axis, const double* in) {
+    if (axis == 0 || !dct_axis_fused_ok(ctx, n0, n1, n2, axis, in, nullptr, 2)) return false;
+    const int LT = fused_lt(ctx, axis == 1 ? n1 : n2, axis, n0, (size_t)n1 * n2, true);
+    if (LT != 16 && LT != 32 && LT != 64 && LT != 128) return false;
+    return (size_t)((n0 + LT - 1) / LT) * (size_t)(axis == 1 ? n2 : n1) <= kPartialDoubles;
+}
+
 // the slab z-solve's half passes: the fused z kernel with ONE merged-middle item per lane (per-lane symbol constants) on a slab whose
 // face buffers are 16-B aligned per line pair
 bool dct_slab_half_ok(bk_ctx* ctx, int n0, int n1, int nl, const double* a, const double* b) {
@@ -973,6 +1007,9 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
                  int fuse_scale, const DctSplit* split, int* dot_blocks, const DctFuse* fz, const DctSlabHalf* sh) {
     FftK P;
     P.dotp = nullptr;
+    const bool nrm = fuse_scale == 3;
+    if (nrm && (!dot_blocks || split || fz || sh || inverse || !dct_axis_nrm_ok(ctx, n0, n1, n2, axis, in)))
+        return set_error(ctx, "dct_axis_fft: the norm-only round trip needs the fused y / z kernel (dct_axis_nrm_ok)");
     P.face_y = nullptr; P.face_d = nullptr; P.phi = nullptr; P.face_Lr = 0; P.slab_a = 0.0; P.slab_hasb = P.slab_hast = 0;
     if (sh) {
         if (!dct_slab_half_ok(ctx, n0, n1, n2, in, out) || axis != 2 || fuse_scale != 0 || split || fz)
@@ -1018,14 +1055,10 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
     P.inverse = inverse; P.in = in; P.out = out; P.twid = twid;
     P.lam0 = lam0; P.lam1 = lam1; P.lam2 = lam2; P.shift = shift;
     P.fuse_scale = fuse_scale == 1 ? 1 : 0;
-    P.roundtrip = fuse_scale == 2 ? 1 : 0;
+    P.roundtrip = fuse_scale >= 2 ? 1 : 0;
     const size_t rows = (size_t)n1 * n2;
-    const bool fused_ok = dct_axis_fused_ok(ctx, n0, n1, n2, axis, in, out, fuse_scale);
-    P.LT = choose_lt(P.N, axis, n0, rows, fused_ok && ctx->opt("dct_lt_wide", 1.0) != 0.0);
-    {
-        const int lt_opt = (int)ctx->opt("dct_lt", 0.0);      // experiment knob: lines per tile of the axis >= 1 passes
-        if (lt_opt >= 2 && axis != 0 && lt_opt <= P.LT) P.LT = lt_opt & ~1;
-    }
+    const bool fused_ok = dct_axis_fused_ok(ctx, n0, n1, n2, axis, in, out, nrm ? 2 : fuse_scale);
+    P.LT = fused_lt(ctx, P.N, axis, n0, rows, fused_ok);
     P.ltbits = -1;
     for (int b = 1; b <= 7; ++b) if ((1 << b) == P.LT) P.ltbits = b;
     unsigned grid;
@@ -1085,7 +1118,10 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, false, true, false, 0, false, false, 512>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, false, false, false, 0, false, false, 512>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, true, true, false, 0, false, false, 512>),
-                             reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, true, false, false, 0, false, false, 512>)};
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, true, false, false, 0, false, false, 512>),
+                             // norm-only round trip
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, false, false, false, 0, false, false, 0, true>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, true, false, false, 0, false, false, 0, true>)};
         for (const void* f : fns) {
             const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
             if (e != hipSuccess) attr_err = e;
@@ -1129,14 +1165,14 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
         const int mode = P.roundtrip ? 2 : (P.inverse ? 1 : 0);
         // the round trip with 512 lanes per tile and the merged middle split over lane pairs (option dct_rt_lanes: 512 / 256):
         // tiles of exactly 512 first-stage items = 256 merged-middle items
-        const bool split512 = mode == 2 && axis != 0 && (size_t)(P.LT / 2) * (P.N / 8) == 512 &&
+        const bool split512 = mode == 2 && !nrm && axis != 0 && (size_t)(P.LT / 2) * (P.N / 8) == 512 &&
                               ctx->opt("dct_rt_lanes", kRoundTripLanesDefault) == 512.0;
-        const bool dot = mode == 2 && dot_blocks && (size_t)grid <= kPartialDoubles && ctx->opt("dct_fused_dot", 1.0) != 0.0;
-        if (dot) { P.dotp = ctx->d_partials; *dot_blocks = (int)grid; }
+        const bool dot = mode == 2 && !nrm && dot_blocks && (size_t)grid <= kPartialDoubles && ctx->opt("dct_fused_dot", 1.0) != 0.0;
+        if (dot || nrm) { P.dotp = ctx->d_partials; *dot_blocks = (int)grid; }      // (nrm: grid <= kPartialDoubles by dct_axis_nrm_ok)
         if (want_turn && !(P.LT == 16 && mode == 1)) return set_error(ctx, "dct_axis_fft: x turnaround off the fused kernel's tiling");
         // compile-time length (option dct_const_len): the z round trip at the 512^3 product path's tiling -- N = 512, LT = 16, axis 2 --
         // and neither the block layout nor the slab halves nor the 512-lane kernel
-        const bool const_len = ctx->opt("dct_const_len", 1.0) != 0.0 && mode == 2 && axis == 2 && P.N == 512 && P.LT == 16 && !split &&
+        const bool const_len = ctx->opt("dct_const_len", 1.0) != 0.0 && mode == 2 && !nrm && axis == 2 && P.N == 512 && P.LT == 16 && !split &&
                                !sh && !split512;
 #define BK_DCT_LAUNCH_SLAB(M, T, S) hipLaunchKernelGGL((dct_fused_kernel<256, M, false, T, false, false, S>), dim3(grid), dim3(256), ldsf, ctx->stream, P)
         if (sh) {
@@ -1153,7 +1189,7 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
         } else if (axis == 0) {
             launch_fused_x(P, grid, ldsf, ctx->stream, mode, ntm, want_turn, want_fz, want_fzs);
         } else {
-            launch_fused_yz(P, grid, ldsf, ctx->stream, mode, ntm, dot, const_len);
+            launch_fused_yz(P, grid, ldsf, ctx->stream, mode, ntm, dot, const_len, nrm);
         }
 #undef BK_DCT_LAUNCH_SLAB
         BK_HIP(ctx, hipGetLastError());
@@ -1177,13 +1213,15 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
                     tmax = std::max(tmax, t);
                 }
             }
-            fprintf(stderr, "dct_trace axis=%d mode=%d tiles=%u span=%.1fus  phases[us]:", axis, P.roundtrip ? 2 : P.inverse, grid,
+            // mode 0 forward, 1 inverse, 2 round trip, 3 norm-only round trip
+            fprintf(stderr, "dct_trace axis=%d mode=%d tiles=%u span=%.1fus  phases[us]:", axis, nrm ? 3 : (P.roundtrip ? 2 : P.inverse), grid,
                     (tmax - tmin) * 0.01);
             for (int i = 1; i < 7; ++i) fprintf(stderr, " %d:%.2f", i, acc[i] / grid * 0.01);
             fprintf(stderr, " const_len=%d\n", const_len ? P.N : 0);
         }
         return 0;
     }
+    if (nrm) return set_error(ctx, "dct_axis_fft: the norm-only round trip off the fused kernel's tiling");
     if (nt == 512) hipLaunchKernelGGL(dct_fft_kernel<512>, dim3(grid), dim3(512), lds, ctx->stream, P);
     else hipLaunchKernelGGL(dct_fft_kernel<256>, dim3(grid), dim3(256), lds, ctx->stream, P);
     BK_HIP(ctx, hipGetLastError());

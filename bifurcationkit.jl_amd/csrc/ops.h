@@ -91,7 +91,9 @@ struct DctFuse {
 };
 int dct_apply(bk_ctx* ctx, DctPlan* p, const double* v, double* out, int* dot_blocks = nullptr, const DctFuse* fz = nullptr);
 // axis pass of the LDS FFT kernels (dct_fast.hip).  fuse_scale 0: plain, 1: forward + inverse symbol, 2: forward,
-// symbol, inverse in one pass.  split (distributed plan, y passes only): the output (forward) / input (inverse) side
+// symbol, inverse in one pass, 3: forward and the per-tile sums of (symbol * spectrum)^2 -- the norm-only round trip: nothing is
+// stored (out is not touched), the partial sums go to ctx->d_partials and their count to *dot_blocks (axis >= 1, dct_axis_nrm_ok;
+// anything else is an error).  split (distributed plan, y passes only): the output (forward) / input (inverse) side
 // uses the all-to-all block layout: element (x, k, other) at kmap[k] + other * plane + x.
 struct DctSplit {
     const unsigned* kmap;
@@ -117,6 +119,7 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
 bool dct_slab_half_ok(bk_ctx* ctx, int n0, int n1, int nl, const double* a, const double* b);
 bool dct_axis_fft_supported(int n);
 bool dct_axis_fused_ok(bk_ctx* ctx, int n0, int n1, int n2, int axis, const double* in, const double* out, int fuse_scale);
+bool dct_axis_nrm_ok(bk_ctx* ctx, int n0, int n1, int n2, int axis, const double* in);
 
 }  // namespace bk
 
@@ -176,6 +179,13 @@ struct bk_op {              // a linear operator on (device vector [+ one host t
     virtual int apply_check(const double* x, const double* xt, double a0, double a1, double* out, double* outt) {
         return apply(x, xt, a0, a1, out, outt);
     }
+    // The NORM of that residual alone, where the operator can have it without forming the residual vector (solver.hip: ShiftPrecOp
+    // with the spectral preconditioner takes it from the spectrum): *done = 1 and *nrm = |b - (a0 + a1 A) x|, else *done = 0 and
+    // nothing was computed.
+    virtual int check_norm(const double* x, double a0, double a1, double* nrm, int* done) { *done = 0; return 0; }
+    // apply_check (unbordered) of the x a check_norm has just returned done = 1 for, with nothing run on this operator in between:
+    // the operator may continue from what check_norm has already computed (the same result, bit for bit)
+    virtual int apply_check_resume(const double* x, double a0, double a1, double* out) { return apply_check(x, nullptr, a0, a1, out, nullptr); }
     // true: GMRES builds its Krylov space on A itself and applies (alpha0, alpha1) to the Hessenberg matrix whatever the flavor
     // (the space of alpha0 + alpha1 A is the space of A; the iterates are the same) -- for operators whose shift costs a stream
     virtual bool hessenberg_shift() const { return false; }
@@ -203,6 +213,12 @@ struct bk_precond {
     // spectral preconditioner lets the axpy ride in its x-forward transform pass (4 array streams instead of 3 + 2), the same values
     // bit for bit (the sum is formed without contraction, as v_axpbyz forms it).
     virtual int apply_dot_pre_axpy(double* y, double c, const double* r, double* out, double* dot);
+    // *nrm2_out = |Pl \ (v + c add)|_2 (add may be NULL).  Default: the sum and Pl \ into scratch, then a norm pass; the spectral
+    // preconditioner takes the norm from the spectrum (Parseval: sum_k sym_k^2 |.^_k|^2) after its forward passes -- no inverse pass,
+    // no result vector -- and lets the sum ride in its x-forward pass where that runs as the fused kernel (nrm2_spectral_ok).
+    virtual int apply_nrm2(const double* v, double c, const double* add, double* nrm2_out);
+    // true if apply_nrm2 runs the spectral form on this plan: looks at options, the communicator and the plan only
+    virtual bool nrm2_spectral_ok() const { return false; }
     // true if this preconditioner is the exact inverse of L1 + *shift I of the problem `prob` (the spectral preconditioner)
     virtual bool is_l1_plus_shift(const bk_problem* prob, double* shift) const { return false; }
     // out = cx x + ct Pl \ (d .* x), d_i = A + u_i (B + C u_i)   (out must not alias x unless pw_fused_ok)

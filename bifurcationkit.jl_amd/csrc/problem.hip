@@ -167,6 +167,17 @@ int bk_op::apply_axpy_dot(const double* x, double a0, double a1, double c, const
     return v_axpy_dot(ctx, n, c, r, out, x, dot);
 }
 
+int bk_precond::apply_nrm2(const double* v, double c, const double* add, double* nrm2_out) {
+    WsGuard ws(ctx);
+    double* t = nullptr;
+    BK_TRY(ws.get(n, &t));
+    if (add) {
+        BK_TRY(v_axpbyz(ctx, n, 1.0, v, c, add, t));
+        BK_TRY(apply(t, t));
+    } else BK_TRY(apply(v, t));
+    return v_nrm2(ctx, n, t, nrm2_out);
+}
+
 int bk_precond::apply_dot_pre_axpy(double* y, double c, const double* r, double* out, double* dot) {
     BK_TRY(v_axpby(ctx, n, c, r, 1.0, y));
     return apply_dot(y, out, dot);

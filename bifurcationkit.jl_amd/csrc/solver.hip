@@ -26,6 +26,10 @@ namespace bk {
 
 namespace {
 
+// The explicit residual check of a converged solve (option gmres_check_spectral): 1 = its norm from the preconditioner's spectrum where
+// ShiftPrecOp::check_norm can have it, 0 = the residual vector through the whole chain.
+constexpr double kCheckSpectralDefault = 1.0;
+
 // First block of a solve on a rearranged operator A = W + theta0 I (ShiftPrecOp, stencil-free form): 0 = powers of A itself,
 // 1 = powers of the literal operator W (see gmres_core: first block).  Option gmres_monomial_shift.
 constexpr double kMonomialShiftDefault = 0.0;
@@ -683,8 +687,20 @@ int gmres_core(bk_ctx* ctx, bk_op* A, const double* b, const double* bt, double*
             } else {
                 // explicit residual r = b - (a0 + a1 A) x, "to ensure that no numerical errors have accumulated"
                 double wt[BK_MAX_BORDER] = {0.0};
-                BK_TRY(A->apply_check(x, nt ? xtail : nullptr, alpha0, alpha1, w, wt));
                 numops += 1;
+                // the norm alone first where the operator has it without the residual vector (bk_op::check_norm: from the spectrum
+                // of the preconditioner, three passes instead of seven); a value that passes is all the solve takes from the check
+                bool spectral_failed = false;
+                if (nt == 0) {
+                    int have = 0;
+                    double bs = 0.0;
+                    BK_TRY(A->check_norm(x, alpha0, alpha1, &bs, &have));
+                    if (have && bs < tol) { beta = bs; res->converged = 1; break; }
+                    spectral_failed = have != 0;
+                }
+                // (a value that failed: the same check through the chain, continued from the stencil pass check_norm has run)
+                if (spectral_failed) BK_TRY(A->apply_check_resume(x, alpha0, alpha1, w));
+                else BK_TRY(A->apply_check(x, nt ? xtail : nullptr, alpha0, alpha1, w, wt));
                 for (int q = 0; q < nt; ++q) rt[q] = bt[q] - wt[q];
                 // the norm first, from b and w as they are (two read streams); the residual VECTOR is only formed when the check fails
                 // and another cycle has to start from it
@@ -707,7 +723,11 @@ int gmres_core(bk_ctx* ctx, bk_op* A, const double* b, const double* bt, double*
                 // and the spectral one cannot pass silently in any flavor.  Within 1.5 x the tolerance the estimate stands
                 // (and is what the solve reports, as IterativeSolvers / Krylov.jl do); beyond it the solve continues from the true residual.
                 double bt_ = 0.0;
-                BK_TRY(A->apply_check(x, nullptr, alpha0, alpha1, w, nullptr));
+                int have = 0;
+                BK_TRY(A->check_norm(x, alpha0, alpha1, &bt_, &have));
+                if (have && bt_ <= 1.5 * tol) { res->converged = 1; break; }
+                if (have) BK_TRY(A->apply_check_resume(x, alpha0, alpha1, w));
+                else BK_TRY(A->apply_check(x, nullptr, alpha0, alpha1, w, nullptr));
                 BK_TRY(v_diff_nrm2(ctx, n, b, w, &bt_));
                 if (bt_ <= 1.5 * tol) { res->converged = 1; break; }
                 ctx->diag.check_mismatch += 1.0;
@@ -797,6 +817,8 @@ struct ShiftPrecOp : bk_op {
         }
         mono_first = ctx->opt("gmres_monomial_shift", kMonomialShiftDefault) != 0.0;
         chain = ctx->opt("dct_x_turnaround", 1.0) != 0.0;
+        // (options, the communicator and the plan only: every rank takes the same decision)
+        spectral_check = ctx->opt("gmres_check_spectral", kCheckSpectralDefault) != 0.0 && P && !Pr && ctx->nranks == 1 && P->nrm2_spectral_ok();
         if (!tmode) return 0;
         // g(u) = l + 2 nu u - 3 u^2 (examples/SH3d.jl:50-53); factor = c0 + cg g = A + u (B + C u)
         const double cg = order == 0 ? 1.0 : a1, c0 = order == 0 ? pl_shift : a0 + a1 * pl_shift;
@@ -812,8 +834,11 @@ struct ShiftPrecOp : bk_op {
     double monomial_shift() const override { return mono_first ? rearranged_origin() : 0.0; }
     bool mono_first = false;      // option gmres_monomial_shift, read once per solve (init_fold)
     bool chain = true;            // option dct_x_turnaround, read once per solve (init_fold)
+    bool spectral_check = false;  // option gmres_check_spectral and what the preconditioner's plan allows, once per solve (init_fold)
+    const double* rhs = nullptr;  // the solve's UNpreconditioned right-hand side (linsolve): b = Pl^-1 rhs
     int apply(const double* x, const double*, double b0, double b1, double* out, double*) override {
         // out = b0 x + b1 * W(x)
+        tmp_valid = false;
         if (tmode) return P->apply_pw(x, pw, b0, b1, out);      // W = T (T'): see above
         return apply_chain(x, b0, b1, out);
     }
@@ -826,12 +851,65 @@ struct ShiftPrecOp : bk_op {
         return P->apply_pw_chain(x, pw, s, cx, b1, outs);
     }
     int apply_check(const double* x, const double*, double c0, double c1, double* out, double*) override {
-        if (!tmode) return apply_chain(x, c0, c1, out);
-        // c0 x + c1 T x through the stencil: T = I + Pl^-1 J (order 0), T' = a1 I + Pl^-1 (a0 + a1 J) (order 1)
-        return order == 0 ? chain_order0(x, c0 + c1, c1, out) : chain_order1(x, c0 + c1 * a1, c1, out);
+        tmp_valid = false;
+        return check_chain(x, c0, c1, out);
     }
+    // apply_check of the x a check_norm has JUST returned done = 1 for: tmp holds the chain's stencil result already
+    int apply_check_resume(const double* x, double c0, double c1, double* out) override {
+        if (!tmp_valid) return set_error(ctx, "apply_check_resume: no check_norm result to continue from");
+        tmp_valid = false;
+        have_tmp = true;
+        const int e = check_chain(x, c0, c1, out);
+        have_tmp = false;
+        return e;
+    }
+    int check_chain(const double* x, double c0, double c1, double* out) {
+        int e;
+        if (!tmode) e = apply_chain(x, c0, c1, out);
+        // c0 x + c1 T x through the stencil: T = I + Pl^-1 J (order 0), T' = a1 I + Pl^-1 (a0 + a1 J) (order 1)
+        else e = order == 0 ? chain_order0(x, c0 + c1, c1, out) : chain_order1(x, c0 + c1 * a1, c1, out);
+        return e;
+    }
+    // |b - (c0 + c1 A) x| of apply_check WITHOUT the residual vector.  b = Pl^-1 rhs, so the residual is Pl^-1 (rhs + c tmp) with tmp the
+    // intermediate the chain itself forms with its one stencil pass, and its norm comes out of the preconditioner's spectrum
+    // (bk_precond::apply_nrm2: Parseval, sum_k sym_k^2 |(Phi' (rhs + c tmp))_k|^2) after the forward passes alone:
+    //   order 0, cx == 0:  tmp = J x, c = -ct                    order 0, fold:  tmp = (ct J + cx Pl) x, c = -1  (chain_order0)
+    //   order 1, b0 == 0:  tmp = (a0 + a1 J) x, c = -b1
+    // Still the original chain -- the stencil kernel's L1 and the spectral symbol -- so a mismatch between the two cannot pass.  tmp
+    // holds exactly what apply_check would put there: when the value fails, gmres_core asks for the chain's result through
+    // apply_check_resume, which continues from it, so the stencil runs once per check as before (tests/test_gpu_stencil_free.py counts
+    // the stencil launches of every solve: at most one per cycle and one).
+    // Everything else (no or a right preconditioner, cx != 0 without fold, ranks, plans off the LDS transforms): *done = 0.
+    bool tmp_valid = false;               // tmp holds the chain intermediate of the last check_norm; cleared by whatever else writes tmp
+    int check_norm(const double* x, double c0, double c1, double* nrm, int* done) override { return check_norm(x, c0, c1, rhs, nrm, done); }
+    int check_norm(const double* x, double c0, double c1, const double* rhs_, double* nrm, int* done) {
+        *done = 0;
+        tmp_valid = false;
+        if (!spectral_check || !rhs_ || !tmp) return 0;
+        double c;
+        if (order == 0) {
+            const double cx = tmode ? c0 + c1 : c0 + c1 * a0, ct = tmode ? c1 : c1 * a1;      // (as apply_check hands them to chain_order0)
+            if (cx != 0.0 && fold) { BK_TRY(J->apply_parts(x, cx * pl_shift, ct - cx, ct, tmp)); c = -1.0; }
+            else if (cx == 0.0) { BK_TRY(J->apply(x, nullptr, 0.0, 1.0, tmp, nullptr)); c = -ct; }
+            else return 0;
+        } else {
+            const double b0 = tmode ? c0 + c1 * a1 : c0, b1 = c1;
+            if (b0 != 0.0) return 0;
+            BK_TRY(J->apply(x, nullptr, a0, a1, tmp, nullptr));
+            c = -b1;
+        }
+        BK_TRY(P->apply_nrm2(rhs_, c, tmp, nrm));
+        tmp_valid = true;
+        *done = 1;
+        return 0;
+    }
+    bool have_tmp = false;        // (apply_check_resume only) the stencil pass of this chain has run: check_norm left its result in tmp
     // out = cx x + ct Pl^-1 J x
     int chain_order0(const double* x, double cx, double ct, double* out) {
+        if (have_tmp) {                        // the forms check_norm takes: cx == 0, or the folded shift
+            BK_TRY(P->apply(tmp, out));
+            return (cx != 0.0 || ct == 1.0) ? 0 : v_scale(ctx, n, ct, out);
+        }
         if (cx != 0.0 && fold) {
             // cx x + ct Pl^-1 J x = Pl^-1 (ct J + cx Pl) x with Pl = L1 + s I and J = -L1 + diag(g):
             //   ct J + cx Pl = (ct - cx) (-L1) + diag(ct g + cx s)
@@ -849,7 +927,7 @@ struct ShiftPrecOp : bk_op {
     }
     // out = b0 x + b1 Pl^-1 (a0 x + a1 J x)
     int chain_order1(const double* x, double b0, double b1, double* out) {
-        BK_TRY(J->apply(x, nullptr, a0, a1, tmp, nullptr));
+        if (!have_tmp) BK_TRY(J->apply(x, nullptr, a0, a1, tmp, nullptr));
         if (b0 == 0.0) {
             BK_TRY(P->apply(tmp, out));
             return b1 == 1.0 ? 0 : v_scale(ctx, n, b1, out);
@@ -1055,6 +1133,7 @@ int linsolve(bk_ctx* ctx, bk_op* J, const double* rhs, double* x, double a0, dou
     W.J = J; W.P = pl; W.a0 = a0; W.a1 = a1; W.order = kk ? 0 : 1; W.tmp = nullptr;
     W.Pr = kk ? nullptr : o.pr;
     BK_TRY(W.init_fold());
+    W.rhs = rhs;
     const double* b = rhs;
     if (pl || W.Pr) BK_TRY(ws.get(J->n, &W.tmp));
     if (W.Pr) BK_TRY(ws.get(J->n, &W.tmp2));
@@ -1214,6 +1293,33 @@ int bk_precond_op_apply(bk_ctx* ctx, bk_precond* pl, bk_op* J, const double* x, 
     if (stencil_free) *stencil_free = W.tmode ? 1 : 0;
     // tmode: W.apply(b0, b1) = b0 x + b1 T x and a0 + a1 Pl^-1 J = (a0 - a1) + a1 T; else the chain a0 x + a1 Pl^-1 (J x)
     return W.tmode ? W.apply(x, nullptr, W.t_alpha0, W.t_alpha1, out, nullptr) : W.apply(x, nullptr, 0.0, 1.0, out, nullptr);
+}
+
+int bk_precond_check_norm(bk_ctx* ctx, bk_precond* pl, bk_op* J, const double* x, const double* rhs, double a0, double a1, int flavor,
+                          double* nrm, int* spectral) {
+    if (!ctx || !pl || !J || !x || !rhs || !nrm) return -1;
+    if (J->ntail != 0) return set_error(ctx, "bk_precond_check_norm: operator must be unbordered");
+    if (flavor != BK_GMRES_KRYLOVKIT && flavor != BK_GMRES_ITERATIVESOLVERS && flavor != BK_GMRES_KRYLOVJL)
+        return set_error(ctx, "bk_precond_check_norm: a GMRES flavor");
+    // the operator exactly as linsolve sets it up, then the check of gmres_core on x
+    WsGuard ws(ctx);
+    ShiftPrecOp W;
+    W.ctx = ctx; W.n = J->n; W.ntail = 0;
+    W.J = J; W.P = pl; W.a0 = a0; W.a1 = a1; W.order = flavor == BK_GMRES_KRYLOVKIT ? 0 : 1; W.tmp = nullptr;
+    BK_TRY(W.init_fold());
+    W.rhs = rhs;
+    BK_TRY(ws.get(J->n, &W.tmp));
+    const double alpha0 = W.tmode ? W.t_alpha0 : 0.0, alpha1 = W.tmode ? W.t_alpha1 : 1.0;
+    int have = 0;
+    BK_TRY(W.check_norm(x, alpha0, alpha1, nrm, &have));
+    if (spectral) *spectral = have;
+    if (have) return 0;
+    double *b = nullptr, *w = nullptr;
+    BK_TRY(ws.get(J->n, &b));
+    BK_TRY(ws.get(J->n, &w));
+    BK_TRY(pl->apply(rhs, b));
+    BK_TRY(W.apply_check(x, nullptr, alpha0, alpha1, w, nullptr));
+    return v_diff_nrm2(ctx, J->n, b, w, nrm);
 }
 
 int bk_abi_version(void) { return BK_ABI_VERSION; }

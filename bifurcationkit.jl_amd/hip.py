@@ -391,6 +391,16 @@ class DCTPreconditioner:
                                                        C.byref(sf)), "bk_precond_op_apply")
         return out, bool(sf.value)
 
+    def check_norm(self, J: "HipJacobian", x: HipVec, rhs: HipVec, a0=0.0, a1=1.0, flavor=0):
+        """The explicit residual check of a left-preconditioned GMRES solve of ``(a0 + a1 J) x = rhs`` in ``flavor`` (0 KrylovKit,
+        1 IterativeSolvers, 2 Krylov.jl): the norm the solve compares with its tolerance.  Returns (norm, spectral): whether it
+        came out of the preconditioner's spectrum (context option ``gmres_check_spectral``) or from the residual vector."""
+        nrm = C.c_double(0.0)
+        sp = C.c_int(0)
+        self.ctx.check(self.ctx.lib.bk_precond_check_norm(self.ctx.h, self.h, J.h, _ptr(x.t), _ptr(rhs.t), float(a0), float(a1),
+                                                         int(flavor), C.byref(nrm), C.byref(sp)), "bk_precond_check_norm")
+        return nrm.value, bool(sp.value)
+
     def __del__(self):
         try:
             if self.h.value:

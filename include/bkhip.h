@@ -212,6 +212,15 @@ int bk_precond_apply(bk_precond* pc, const double* v, double* out);   /* out = P
  * then Pl).  *stencil_free (optional) reports which form ran.  out must not alias x.                                        */
 int bk_precond_op_apply(bk_ctx* ctx, bk_precond* pl, bk_op* J, const double* x, double a0, double a1, double* out,
                         int* stencil_free);
+/* Its twin for the explicit residual check of a left-preconditioned GMRES solve of (a0 + a1 J) x = rhs in `flavor`
+ * (BK_GMRES_KRYLOVKIT / _ITERATIVESOLVERS / _KRYLOVJL): *nrm = the value the solve compares with its tolerance once the Arnoldi
+ * estimate has converged, |Pl \ rhs - a0 x - a1 Pl \ (J x)| (KrylovKit), |Pl \ (rhs - (a0 + a1 J) x)| (the others).  With the
+ * spectral preconditioner on the LDS transform kernels (single rank, round trip on) the norm comes out of the spectrum --
+ * Pl \ of ONE vector rhs - (...) x formed from the chain's own stencil pass, forward transforms only, sum_k sym_k^2 |.^_k|^2 -- instead of
+ * the residual vector through the whole chain (context option "gmres_check_spectral", default 1; 0 = the chain).  *spectral
+ * (optional) reports which path ran.                                                                                          */
+int bk_precond_check_norm(bk_ctx* ctx, bk_precond* pl, bk_op* J, const double* x, const double* rhs, double a0, double a1, int flavor,
+                          double* nrm, int* spectral);
 
 /* ------------------------------------------------------------------ linear solver ----------
  * (ls::AbstractLinearSolver)(J, rhs; a0, a1) -> (x, success, niter): src/LinearSolver.jl:12.   */

@@ -286,6 +286,19 @@ function HipCGLBlockPreconditioner(prob::HipProblem, a::Real, b::Real)
     finalizer(x -> ccall((:bk_precond_destroy, libbkhip[]), Cint, (Ptr{Cvoid},), x.h), P)
 end
 _plh(::Nothing) = C_NULL
+"""
+The explicit residual check of a left-preconditioned GMRES solve of `(a0 + a1 J) x = rhs` in `flavor` (0 KrylovKit, 1 IterativeSolvers,
+2 Krylov.jl): `(norm, spectral)`, the value the solve compares with its tolerance and whether it came out of the preconditioner's
+spectrum (context option `gmres_check_spectral`) or from the residual vector through the whole chain.
+"""
+function precond_check_norm(P::HipDCTPreconditioner, J, x, rhs; a0::Real = 0.0, a1::Real = 1.0, flavor::Integer = 0)
+    nrm = Ref{Cdouble}(0.0)
+    sp = Ref{Cint}(0)
+    check(P.prob.ctx, ccall((:bk_precond_check_norm, libbkhip[]), Cint,
+                            (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cdouble, Cdouble, Cint, Ref{Cdouble}, Ref{Cint}),
+                            P.prob.ctx.h, P.h, J.h, x.p, rhs.p, a0, a1, flavor, nrm, sp), "bk_precond_check_norm")
+    return nrm[], sp[] != 0
+end
 _plh(P::Union{HipDCTPreconditioner, HipLaplacePreconditioner, HipCGLBlockPreconditioner}) = P.h
 
 # ------------------------------------------------------------------------------------------------ linear solver

@@ -23,7 +23,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bifurcationkit.jl_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-ffp-contract=off"]
-PARAMS = ["NT", "MODE", "AX0", "NTM", "DOT", "FZ", "SLAB", "FZS", "TURN", "CN"]
+PARAMS = ["NT", "MODE", "AX0", "NTM", "DOT", "FZ", "SLAB", "FZS", "TURN", "CN", "NRM"]
+CN = PARAMS.index("CN")
 
 
 def compile_asm(out):
@@ -73,7 +74,7 @@ def stats(k):
 def label(args):
     a = dict(zip(PARAMS, args))
     s = "<%d,%d,%s" % (a["NT"], a["MODE"], "AX0" if a["AX0"] else ("z" if a["MODE"] == 2 else "y"))
-    for f in ("NTM", "DOT", "FZ", "FZS", "TURN"):
+    for f in ("NTM", "DOT", "FZ", "FZS", "TURN", "NRM"):
         if a[f]:
             s += "," + f
     if a["SLAB"]:
@@ -102,7 +103,7 @@ def main():
     hdr = "%-28s %5s %5s %5s %4s %4s %4s %3s" % ("instantiation", "VALU", "f64", "int", "rcp", "VGPR", "scr", "occ")
     print("All fused-kernel instantiations (runtime length, CN = 0)")
     print(hdr)
-    for args in sorted(k for k in kernels if k[-1] == 0):
+    for args in sorted(k for k in kernels if k[CN] == 0):
         s = stats(kernels[args])
         print("%-28s %5d %5d %5d %4d %4d %4d %3d" % (label(args), s["valu"], s["f64"], s["other"], s["rcp"], s["vgpr"],
                                                    s["scratch"], s["occ"]))
@@ -111,8 +112,8 @@ def main():
     print("%-28s %11s %11s %11s %9s %7s %3s  %s" % ("instantiation", "VALU 0/512", "f64 0/512", "int 0/512", "int cut", "VGPR",
                                                    "scr", "largest non-f64 VALU ops at CN = 512"))
     diff = []
-    for args in sorted(k for k in kernels if k[-1] == 512):
-        fb = args[:-1] + (0,)
+    for args in sorted(k for k in kernels if k[CN] == 512):
+        fb = args[:CN] + (0,) + args[CN + 1:]
         s1 = stats(kernels[args])
         if fb not in kernels:
             bad.append("%s: no fallback" % label(args))
