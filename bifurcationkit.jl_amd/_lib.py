@@ -149,6 +149,7 @@ SIGNATURES = {
     "bk_gmres_default_opts": (None, [C.POINTER(GmresOpts), I]),
     "bk_gmres": (I, [VP, VP, VP, VP, D, D, C.POINTER(GmresOpts), VP, c_int_p, c_int_p, c_double_p]),
     "bk_gmres2": (I, [VP, VP, VP, VP, VP, VP, D, D, C.POINTER(GmresOpts), VP, c_int_p, c_int_p]),
+    "bk_palc_update": (I, [VP, SZ, D, VP, VP, VP]),
     "bk_bls_bordering": (I, [VP, VP, VP, VP, D, VP, D, D, D, I, D, D, C.POINTER(BorderingOpts),
                              C.POINTER(GmresOpts), VP, VP, c_double_p, c_int_p, c_int_p]),
     "bk_bls_matrixfree": (I, [VP, VP, VP, VP, D, VP, D, D, D, I, D, D, C.POINTER(GmresOpts), VP, c_double_p,

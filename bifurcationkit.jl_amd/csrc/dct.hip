@@ -473,8 +473,9 @@ int dct_apply(bk_ctx* ctx, DctPlan* p, const double* v, double* out, int* dot_bl
     auto axis_pass = [&](int a, int inverse, const double* in, double* o, int fuse) -> int {
         // the fused pointwise work (DctFuse) rides in the first pass (input side: in == v) and the last one (output side: o == out)
         const DctFuse* f = (fz && a == 0 && ((!inverse && in == v && (fz->u || fz->add)) || (inverse && o == out && fz->xadd))) ? fz : nullptr;
-        // one read + one write of the array per axis pass (+ the fused stream; + the stored sum of the pre-axpy form)
-        ProfScope ps(ctx, "dct_pass", (f ? (!inverse && fz->add ? 32.0 : 24.0) : 16.0) * p->total);
+        // one read + one write of the array per axis pass (+ the fused stream; + the stored sum of the pre-axpy form or the stored
+        // scaled source of a cycle start)
+        ProfScope ps(ctx, "dct_pass", (f ? (!inverse && ((fz->add && fz->store) || fz->src) ? 32.0 : 24.0) : 16.0) * p->total);
         if (use_fft && p->twid[a]) {
             return dct_axis_fft(ctx, n0, n1, n2, a, inverse, p->twid[a], in, o, p->lam[0], p->lam[1],
                                 p->ndim == 3 ? p->lam[2] : nullptr, p->shift, fuse, nullptr, fuse == 2 ? dot_blocks : nullptr, f);
@@ -543,7 +544,14 @@ static int dct_apply_pw_chain(bk_ctx* ctx, DctPlan* p, const double* x, const Dc
     };
     DctFuse f0;
     f0.u = d.u; f0.A = d.A; f0.B = d.B; f0.C = d.C;
-    BK_TRY(pass(0, 0, x, p->t1, 0, &f0, 24.0));                       // X_0 = x-forward(d .* x)
+    if (d.src) {
+        // cycle start: x = d.src_scale * d.src is written by this pass (reads src and u, writes x and X_0)
+        DctFuse fs = f0;
+        fs.src = d.src; fs.src_scale = d.src_scale; fs.src_store = d.src_store;
+        BK_TRY(pass(0, 0, x, p->t1, 0, &fs, 32.0));
+    } else {
+        BK_TRY(pass(0, 0, x, p->t1, 0, &f0, 24.0));                   // X_0 = x-forward(d .* x)
+    }
     for (int i = 0; i < s; ++i) {
         double* bufs[2] = {p->t1, p->t2};
         const double* src = p->t1;
@@ -847,9 +855,15 @@ struct ShDctPrecond : bk_precond {
                dct_axis_fused_ok(ctx, plan->n[0], plan->n[1], nzl, 0, plan->t2, const_cast<double*>(out), 0);
     }
     bool pw_plan_ok() const override { return plan && plan->t1 && plan->t2 && pw_fused_ok(plan->t1, plan->t1, plan->t2); }
+    // the scaled source of a cycle start can ride in the x-forward pass of an application of x: the single-rank plan proper (neither
+    // distributed nor the slab emulation), x the array it stores to, and src readable by the fused kernel
+    bool pw_src_ok(const double* x, const DctFuse& d) const {
+        return !plan->dist && !plan->slab_ok && ctx->nranks == 1 && x == d.src_store && d.src != x && pw_fused_ok(d.src, d.u, x);
+    }
     int apply_pw(const double* x, const DctFuse& d, double cx, double ct, double* out) override {
         if (!pw_fused_ok(x, d.u, out) || ctx->opt("dct_fuse_pw", 1.0) == 0.0) return bk_precond::apply_pw(x, d, cx, ct, out);
         DctFuse f = d;
+        if (f.src && !pw_src_ok(x, f)) BK_TRY(pw_src_first(f));
         f.xadd = nullptr; f.cx = 0.0; f.ct = 1.0;
         const bool scale_after = cx == 0.0 && ct != 1.0;              // (rare: no x term but a scale -- not worth a kernel variant)
         if (cx != 0.0) { f.xadd = x; f.cx = cx; f.ct = ct; }
@@ -865,7 +879,9 @@ struct ShDctPrecond : bk_precond {
         for (int i = 0; ok && i < s; ++i)
             ok = (cx[i] != 0.0 || ct == 1.0) && pw_fused_ok(i == 0 ? x : outs[i - 1], d.u, outs[i]) && outs[i] != (i == 0 ? x : outs[i - 1]);
         if (!ok) return bk_precond::apply_pw_chain(x, d, s, cx, ct, outs);
-        return dct_apply_pw_chain(ctx, plan, x, d, s, cx, ct, outs);
+        DctFuse f = d;
+        if (f.src && !pw_src_ok(x, f)) BK_TRY(pw_src_first(f));
+        return dct_apply_pw_chain(ctx, plan, x, f, s, cx, ct, outs);
     }
     int apply_dot_pre_axpy(double* y, double c, const double* r, double* out, double* dot) override {
         // (plan->slab_ok: the cost model's slab emulation routes through dct_apply_slab, which only knows the stencil-free operator's fusions)
@@ -891,8 +907,8 @@ struct ShDctPrecond : bk_precond {
         const int last = plan->ndim - 1;
         return dct_axis_nrm_ok(ctx, plan->n[0], plan->n[1], plan->n[2], last, last == 1 ? plan->t1 : plan->t2);
     }
-    int apply_nrm2(const double* v, double c, const double* add, double* nrm2_out) override {
-        if (!nrm2_spectral_ok()) return bk_precond::apply_nrm2(v, c, add, nrm2_out);
+    int apply_nrm2(const double* v, double c, const double* add, double* nrm2_out, bool store_sum) override {
+        if (!nrm2_spectral_ok()) return bk_precond::apply_nrm2(v, c, add, nrm2_out, store_sum);
         const int n0 = plan->n[0], n1 = plan->n[1], n2 = plan->n[2], last = plan->ndim - 1;
         auto pass = [&](int a, const double* in, double* o, int fuse, int* nb, double bytes, const DctFuse* f) -> int {
             ProfScope ps(ctx, "dct_pass", bytes * plan->total);
@@ -904,11 +920,12 @@ struct ShDctPrecond : bk_precond {
         DctFuse f;
         const DctFuse* f0 = nullptr;
         if (add) {
-            // v + c add rides in the x-forward pass where that is the fused kernel (FZS: the sum is formed per sample and also stored --
-            // into t2, which nothing reads before the next pass overwrites it); else one axpbyz pass into t2 first
+            // v + c add rides in the x-forward pass where that is the fused kernel (FZS: the sum is formed per sample and enters the
+            // transform; nothing reads it as a vector, so it is not stored -- store_sum, option gmres_check_nostore = 0, writes it into t2
+            // as the pass did before, which the next pass overwrites); else one axpbyz pass into t2 first
             if (ctx->opt("dct_fuse_pw", 1.0) != 0.0 && ((((uintptr_t)v) | ((uintptr_t)add)) & 15) == 0 &&
                 dct_axis_fused_ok(ctx, n0, n1, n2, 0, v, plan->t1, 0)) {
-                f.add = add; f.cadd = c; f.store = plan->t2;
+                f.add = add; f.cadd = c; f.store = store_sum ? plan->t2 : nullptr; f.nostore = !store_sum;
                 f0 = &f;
             } else {
                 BK_TRY(v_axpbyz(ctx, n, 1.0, v, c, add, plan->t2));
@@ -916,7 +933,7 @@ struct ShDctPrecond : bk_precond {
             }
         }
         for (int a = 0; a < last; ++a) {
-            BK_TRY(pass(a, src, bufs[a], 0, nullptr, (a == 0 && f0) ? 32.0 : 16.0, a == 0 ? f0 : nullptr));
+            BK_TRY(pass(a, src, bufs[a], 0, nullptr, (a == 0 && f0) ? (f.store ? 32.0 : 24.0) : 16.0, a == 0 ? f0 : nullptr));
             src = bufs[a];
         }
         int nb = 0;

@@ -58,7 +58,7 @@ struct FftK {
     // sample's own index; inverse -- the stored value is fz_ct * result + fz_cx * fz_v[same index]
     const double* fz_v;
     double fzA, fzB, fzC, fz_cx, fz_ct;
-    double* fz_store;         // FZS (forward): the sample + fz_cx * fz_v[same index] is what gets transformed, and it is stored here
+    double* fz_store;         // FZS (forward): the sample + fz_cx * fz_v[same index] is what gets transformed, and it is stored here (NULL: not stored)
     // TURN (x inverse, then the next x forward in the same tile residency): the stored inverse result, multiplied by
     // fzA + u (fzB + fzC u) with u = turn_u[same index], is transformed forward and the spectrum is stored to turn_out
     const double* turn_u;
@@ -397,16 +397,20 @@ __device__ __forceinline__ c2 lane_xor1(c2 v) { c2 r; r.x = lane_xor1(v.x); r.y 
 // today's code generation, checked on the device by tests/test_gpu_dct_const_len.py, not guaranteed by construction.  (The x passes
 // at N = 512 did come out different in the last bit, and the y passes ran slower; both stay at the runtime length --
 // profiles/r8_const_len_isa.txt.)
+// SRC (with FZ, MODE 0): the first x-forward pass of a GMRES cycle (solver.hip: start_cycle, option gmres_fuse_v0).  The samples are
+// read from the cycle's residual, multiplied by fz_cx = 1 / beta, stored to fz_store -- the basis vector V[0] the plain FZ pass would
+// have read -- and go on through the FZ factor and the transform: one pass instead of the scale pass and the FZ pass.
 // NRM (with MODE 2, runtime length): the norm-only round trip of a solve's explicit residual check (dct.hip: ShDctPrecond::apply_nrm2).
 // The tile runs the first stage, the forward middle stages and the merged middle's forward half, and sums sym_k^2 |v^_k|^2 -- by
 // Parseval |M^-1 v|^2 of this tile's lines -- into P.dotp[workgroup] exactly as DOT sums sym_k |v^_k|^2: same symbol, same rcp_nr,
 // fixed summation order, no atomics.  No inverse stages, no last stage, no global store: 8 B/point.
 template <int NT, int MODE, bool AX0, bool NTM, bool DOT = false, bool FZ = false, int SLAB = 0, bool FZS = false, bool TURN = false,
-          int CN = 0, bool NRM = false>   // MODE 0: forward, 1: inverse, 2: forward - symbol - inverse (AX0: 0 / 1 only)
+          int CN = 0, bool NRM = false, bool SRC = false>   // MODE 0: forward, 1: inverse, 2: forward - symbol - inverse (AX0: 0 / 1 only)
 __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P) {
     constexpr bool SPLIT = NT == 512;
     static_assert(!TURN || (MODE == 1 && AX0 && !DOT && SLAB == 0 && !FZS && !SPLIT), "TURN: the x inverse pass only");
     static_assert(!FZS || (FZ && MODE == 0), "FZS: the x-forward pass only");
+    static_assert(!SRC || (FZ && MODE == 0 && !FZS && !TURN), "SRC: the plain FZ x-forward pass only");
     static_assert(!SPLIT || (MODE == 2 && !AX0 && !FZ && SLAB == 0), "512 lanes: the z / y round trip only");
     static_assert(!FZ || (AX0 && MODE != 2), "FZ: x passes only");
     static_assert(SLAB == 0 || (!AX0 && !FZ && !DOT && ((SLAB == 1 && MODE == 0) || (SLAB == 2 && MODE == 1))), "SLAB: z halves only");
@@ -651,10 +655,23 @@ __global__ void __launch_bounds__(NT, NT == 512 ? 4 : 2) dct_fused_kernel(FftK P
                                                const int t = FZ ? s : 0;
                                                ea = __dadd_rn(__dmul_rn(P.fz_cx, qfa[t].x), ea); oa = __dadd_rn(__dmul_rn(P.fz_cx, qfa[t].y), oa);
                                                eb = __dadd_rn(__dmul_rn(P.fz_cx, qfb[t].x), eb); ob = __dadd_rn(__dmul_rn(P.fz_cx, qfb[t].y), ob);
-                                               double* srow = P.fz_store + tile_base(tile) + (size_t)(2 * (tid >> hbits)) * lstride;
-                                               st16(srow + 2 * j, ea, oa);
-                                               st16(srow + lstride + 2 * j, eb, ob);
+                                               // (no store array -- the explicit residual check of a GMRES solve, dct.hip: apply_nrm2 -- the
+                                               // sum only enters the transform: a wave-uniform test)
+                                               if (P.fz_store) {
+                                                   double* srow = P.fz_store + tile_base(tile) + (size_t)(2 * (tid >> hbits)) * lstride;
+                                                   st16(srow + 2 * j, ea, oa);
+                                                   st16(srow + lstride + 2 * j, eb, ob);
+                                               }
                                            } else if (FZ || TURN) {
+                                               if (SRC) {
+                                                   // the samples come from the source vector (P.in): one rounded product with the scalar, as
+                                                   // v_axpbyz forms a * x, stored to the array the plain FZ pass reads and used from registers
+                                                   ea = __dmul_rn(P.fz_cx, ea); oa = __dmul_rn(P.fz_cx, oa);
+                                                   eb = __dmul_rn(P.fz_cx, eb); ob = __dmul_rn(P.fz_cx, ob);
+                                                   double* srow = P.fz_store + tile_base(tile) + (size_t)(2 * (tid >> hbits)) * lstride;
+                                                   st16(srow + 2 * j, ea, oa);
+                                                   st16(srow + lstride + 2 * j, eb, ob);
+                                               }
                                                const int t = (FZ || TURN) ? s : 0;
                                                const c2 wa = TURN ? ufa[TURN ? t : 0] : qfa[FZ ? t : 0];
                                                const c2 wb = TURN ? ufb[TURN ? t : 0] : qfb[FZ ? t : 0];
@@ -927,17 +944,18 @@ inline int choose_lt(int N, int axis, int n0, size_t rows, bool wide = false) {
 // The 256-lane fused passes: x forward / inverse (plain, FZ, FZS, TURN shifted / unshifted), y forward / inverse and the z round trip
 // with and without DOT at the runtime length (CN = 0); the z round trip also at the compile-time length (CN = 512) -- NTM on and off.
 // The norm-only round trip (NRM) at the runtime length only.  The slab halves and the 512-lane round trip are launched by the caller.
-template <int MODE, bool AX0, bool DOT, bool FZ, bool FZS, bool TURN, int CN, bool NRM = false>
+template <int MODE, bool AX0, bool DOT, bool FZ, bool FZS, bool TURN, int CN, bool NRM = false, bool SRC = false>
 void launch_fused_ntm(const FftK& P, unsigned grid, size_t lds, hipStream_t st, bool ntm) {
-    if (ntm) hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, true, DOT, FZ, 0, FZS, TURN, CN, NRM>), dim3(grid), dim3(256), lds, st, P);
-    else hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, false, DOT, FZ, 0, FZS, TURN, CN, NRM>), dim3(grid), dim3(256), lds, st, P);
+    if (ntm) hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, true, DOT, FZ, 0, FZS, TURN, CN, NRM, SRC>), dim3(grid), dim3(256), lds, st, P);
+    else hipLaunchKernelGGL((dct_fused_kernel<256, MODE, AX0, false, DOT, FZ, 0, FZS, TURN, CN, NRM, SRC>), dim3(grid), dim3(256), lds, st, P);
 }
 
-void launch_fused_x(const FftK& P, unsigned grid, size_t lds, hipStream_t st, int mode, bool ntm, bool turn, bool fz, bool fzs) {
+void launch_fused_x(const FftK& P, unsigned grid, size_t lds, hipStream_t st, int mode, bool ntm, bool turn, bool fz, bool fzs, bool src) {
     //                                        MODE AX0    DOT    FZ     FZS    TURN
     if (turn && fz) launch_fused_ntm<1, true, false, true, false, true, 0>(P, grid, lds, st, ntm);
     else if (turn) launch_fused_ntm<1, true, false, false, false, true, 0>(P, grid, lds, st, ntm);
     else if (fzs) launch_fused_ntm<0, true, false, true, true, false, 0>(P, grid, lds, st, ntm);
+    else if (src) launch_fused_ntm<0, true, false, true, false, false, 0, false, true>(P, grid, lds, st, ntm);
     else if (fz && mode == 1) launch_fused_ntm<1, true, false, true, false, false, 0>(P, grid, lds, st, ntm);
     else if (fz) launch_fused_ntm<0, true, false, true, false, false, 0>(P, grid, lds, st, ntm);
     else if (mode == 1) launch_fused_ntm<1, true, false, false, false, false, 0>(P, grid, lds, st, ntm);
@@ -1031,14 +1049,19 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
     // the pointwise work this pass is asked to take in: the factor (or the pre-axpy) on a forward pass, the axpy on an inverse one
     const bool want_fzs = fz && !inverse && fz->add != nullptr;
     const bool want_fz = fz && (inverse ? fz->xadd != nullptr : (fz->u != nullptr || want_fzs));
+    // cycle start (DctFuse::src): the samples come from src, scaled, and are stored to src_store = `in`, the array this pass stands in for
+    const bool want_src = fz && !inverse && fz->src != nullptr;
+    if (want_src && (!want_fz || want_fzs || fz->src_store != in || fz->src == in || (((uintptr_t)fz->src) & 15) != 0))
+        return set_error(ctx, "dct_axis_fft: the scaled source needs the plain fused x-forward pass on the stored array");
     if (want_fz) {
         if (axis != 0 || fuse_scale != 0 || split || !dct_axis_fused_ok(ctx, n0, n1, n2, 0, in, out, 0) ||
             (((uintptr_t)(inverse ? fz->xadd : (want_fzs ? fz->add : fz->u))) & 15) != 0 ||
-            (want_fzs && (fz->u != nullptr || fz->store == nullptr || (((uintptr_t)fz->store) & 15) != 0)))
+            (want_fzs && (fz->u != nullptr || (fz->store == nullptr) != fz->nostore || (((uintptr_t)fz->store) & 15) != 0)))
             return set_error(ctx, "dct_axis_fft: fused pointwise work needs the fused x-axis kernel (pw_fused_ok)");
         if (inverse) { P.fz_v = fz->xadd; P.fz_cx = fz->cx; P.fz_ct = fz->ct; }
         else if (want_fzs) { P.fz_v = fz->add; P.fz_cx = fz->cadd; P.fz_store = fz->store; }
         else { P.fz_v = fz->u; P.fzA = fz->A; P.fzB = fz->B; P.fzC = fz->C; }
+        if (want_src) { P.fz_cx = fz->src_scale; P.fz_store = fz->src_store; }
     }
     if (dot_blocks) *dot_blocks = 0;
     P.kmap = nullptr; P.split_plane = 0; P.split = 0;
@@ -1052,7 +1075,7 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
     P.bits = 0;
     while ((1 << P.bits) < P.N) ++P.bits;
     if (!dct_axis_fft_supported(P.N)) return set_error(ctx, "dct_axis_fft: N=%d unsupported", P.N);
-    P.inverse = inverse; P.in = in; P.out = out; P.twid = twid;
+    P.inverse = inverse; P.in = want_src ? fz->src : in; P.out = out; P.twid = twid;
     P.lam0 = lam0; P.lam1 = lam1; P.lam2 = lam2; P.shift = shift;
     P.fuse_scale = fuse_scale == 1 ? 1 : 0;
     P.roundtrip = fuse_scale >= 2 ? 1 : 0;
@@ -1114,6 +1137,9 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, false, false, true, 0, false, true>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, true, false, false, 0, false, true>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 1, true, true, false, true, 0, false, true>),
+                             // scaled source (launch_fused_x)
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 0, true, false, false, true, 0, false, false, 0, false, true>),
+                             reinterpret_cast<const void*>(dct_fused_kernel<256, 0, true, true, false, true, 0, false, false, 0, false, true>),
                              // compile-time length (launch_fused_yz)
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, false, true, false, 0, false, false, 512>),
                              reinterpret_cast<const void*>(dct_fused_kernel<256, 2, false, false, false, false, 0, false, false, 512>),
@@ -1187,7 +1213,7 @@ int dct_axis_fft(bk_ctx* ctx, int n0, int n1, int n2, int axis, int inverse, con
                 else hipLaunchKernelGGL((dct_fused_kernel<512, 2, false, false>), dim3(grid), dim3(512), ldsf, ctx->stream, P);
             }
         } else if (axis == 0) {
-            launch_fused_x(P, grid, ldsf, ctx->stream, mode, ntm, want_turn, want_fz, want_fzs);
+            launch_fused_x(P, grid, ldsf, ctx->stream, mode, ntm, want_turn, want_fz, want_fzs, want_src);
         } else {
             launch_fused_yz(P, grid, ldsf, ctx->stream, mode, ntm, dot, const_len, nrm);
         }

@@ -82,12 +82,22 @@ struct DctFuse {
     double cx = 0.0, ct = 1.0;
     // round 6 (MINRES: bk_precond::apply_dot_pre_axpy): the x-forward pass transforms in[i] + cadd * add[i] and stores that combined
     // vector to store[i] (may be the input array itself) -- the pass y <- y + c r of the Lanczos recurrence rides in the transform
+    // (nostore: the sum only enters the transform and store must be NULL -- the explicit residual check of a GMRES solve, option
+    // gmres_check_nostore; without the flag a missing store array is an error, so that no caller loses its vector silently)
     const double* add = nullptr;
     double cadd = 0.0;
     double* store = nullptr;
+    bool nostore = false;
     // x turnaround (bk_precond::apply_pw_chain, dct.hip: dct_apply_pw_chain): the x-INVERSE pass also multiplies what it stores by
     // A + u (B + C u) and runs the next application's x-forward pass on it in the same tile residency, spectrum to xfwd
     double* xfwd = nullptr;
+    // cycle start of GMRES (solver.hip: start_cycle, option gmres_fuse_v0): the x-forward pass of the FIRST application reads its
+    // samples from src, multiplies them by src_scale (one rounded product, as v_axpbyz forms a * x), stores that to src_store -- which
+    // must be the application's input array x, not yet written -- and goes on as with u: V[0] = r / beta is written by the pass that
+    // would have read it.  Whoever cannot run that pass writes src_store first (bk_precond::pw_src_first) and goes on without it.
+    const double* src = nullptr;
+    double src_scale = 1.0;
+    double* src_store = nullptr;
 };
 int dct_apply(bk_ctx* ctx, DctPlan* p, const double* v, double* out, int* dot_blocks = nullptr, const DctFuse* fz = nullptr);
 // axis pass of the LDS FFT kernels (dct_fast.hip).  fuse_scale 0: plain, 1: forward + inverse symbol, 2: forward,
@@ -199,6 +209,13 @@ struct bk_op {              // a linear operator on (device vector [+ one host t
     // ritz_shifts) -- the order relative to T's own origin truncated a block per solve on running branches (measured in round 5,
     // DESIGN 3) -- so that the two options can be set independently
     virtual double rearranged_origin() const { return 0.0; }
+    // GMRES cycle start: the NEXT application (apply / apply_block) will be of x = dst, and dst = scale * src has not been written
+    // yet.  true: the operator has taken note and writes dst itself, in or before that application, exactly as
+    // v_axpbyz(scale, src -> dst) would (solver.hip: ShiftPrecOp lets the preconditioner's first transform pass do it); false:
+    // nothing noted, the caller writes dst.
+    virtual bool arm_v0(const double* src, double scale, double* dst) { return false; }
+    // ... and forget it again (a cycle start that failed before the application ran)
+    virtual void disarm_v0() {}
 };
 
 struct bk_precond {
@@ -216,14 +233,18 @@ struct bk_precond {
     // *nrm2_out = |Pl \ (v + c add)|_2 (add may be NULL).  Default: the sum and Pl \ into scratch, then a norm pass; the spectral
     // preconditioner takes the norm from the spectrum (Parseval: sum_k sym_k^2 |.^_k|^2) after its forward passes -- no inverse pass,
     // no result vector -- and lets the sum ride in its x-forward pass where that runs as the fused kernel (nrm2_spectral_ok).
-    virtual int apply_nrm2(const double* v, double c, const double* add, double* nrm2_out);
+    // (store_sum = false, option gmres_check_nostore: the fused x-forward pass does not write the sum anywhere, 24 instead of 32 B/point)
+    virtual int apply_nrm2(const double* v, double c, const double* add, double* nrm2_out, bool store_sum = true);
     // true if apply_nrm2 runs the spectral form on this plan: looks at options, the communicator and the plan only
     virtual bool nrm2_spectral_ok() const { return false; }
     // true if this preconditioner is the exact inverse of L1 + *shift I of the problem `prob` (the spectral preconditioner)
     virtual bool is_l1_plus_shift(const bk_problem* prob, double* shift) const { return false; }
     // out = cx x + ct Pl \ (d .* x), d_i = A + u_i (B + C u_i)   (out must not alias x unless pw_fused_ok)
     // Default: a pointwise pass, apply, an axpby; the spectral preconditioner fuses both into its first / last transform pass.
+    // d.src (DctFuse: the scaled source of a GMRES cycle start) holds for the first application only; x is then d.src_store.
     virtual int apply_pw(const double* x, const bk::DctFuse& d, double cx, double ct, double* out);
+    // the scale pass d.src_store = d.src_scale * d.src as a pass of its own, and d.src cleared (no-op without d.src)
+    int pw_src_first(bk::DctFuse& d);
     virtual bool pw_fused_ok(const double* x, const double* u, const double* out) const { return false; }
     // A chain of s such applications, each on the previous one's output: x_0 = x, outs[i] = cx[i] x_i + ct Pl \ (d .* x_i),
     // x_{i+1} = outs[i] (the Newton-basis block of solver.hip: arnoldi_block; outs[i] must not alias x_i).  Default: s apply_pw
@@ -275,9 +296,11 @@ int linsolve(bk_ctx* ctx, bk_op* J, const double* rhs, double* x, double a0, dou
 int linsolve2(bk_ctx* ctx, bk_op* J, const double* rhs1, double* x1, const double* rhs2, double* x2, double a0, double a1,
               const bk_gmres_opts& o, bk_precond* pl, GmresResult* r1, GmresResult* r2);
 // BorderingBLS (src/LinearBorderSolver.jl:88-166) on an unbordered operator (solver.hip; bk_bls_bordering without the checks)
+// xnew (optional, check_precision off only): also xnew <- xnew - dX in the tail pass; dX then holds x1 without the dl term
 int bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R, double nn,
                   double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_bordering_opts& bo,
-                  const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2]);
+                  const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2],
+                  double* xnew = nullptr);
 // callback(state; fromNewton) of the Newton correctors (solver.hip, minaug.h): the cbMaxNorm veto, then the user's function;
 // 0 = stop
 int newton_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear, double p,

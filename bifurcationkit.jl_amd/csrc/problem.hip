@@ -167,7 +167,7 @@ int bk_op::apply_axpy_dot(const double* x, double a0, double a1, double c, const
     return v_axpy_dot(ctx, n, c, r, out, x, dot);
 }
 
-int bk_precond::apply_nrm2(const double* v, double c, const double* add, double* nrm2_out) {
+int bk_precond::apply_nrm2(const double* v, double c, const double* add, double* nrm2_out, bool) {
     WsGuard ws(ctx);
     double* t = nullptr;
     BK_TRY(ws.get(n, &t));
@@ -183,8 +183,17 @@ int bk_precond::apply_dot_pre_axpy(double* y, double c, const double* r, double*
     return apply_dot(y, out, dot);
 }
 
-int bk_precond::apply_pw(const double* x, const bk::DctFuse& d, double cx, double ct, double* out) {
-    // the separate passes: t = d .* x ; t = Pl \ t ; out = cx x + ct t
+int bk_precond::pw_src_first(bk::DctFuse& d) {
+    if (!d.src) return 0;
+    const double* src = d.src;
+    d.src = nullptr;
+    return v_axpbyz(ctx, n, d.src_scale, src, 0.0, nullptr, d.src_store);
+}
+
+int bk_precond::apply_pw(const double* x, const bk::DctFuse& d0, double cx, double ct, double* out) {
+    // the separate passes: t = d .* x ; t = Pl \ t ; out = cx x + ct t   (a scaled source: its pass first)
+    bk::DctFuse d = d0;
+    BK_TRY(pw_src_first(d));
     if (cx == 0.0) {
         BK_TRY(v_pw_scale(ctx, n, x, d.u, d.A, d.B, d.C, out));
         BK_TRY(apply(out, out));
@@ -200,7 +209,9 @@ int bk_precond::apply_pw(const double* x, const bk::DctFuse& d, double cx, doubl
 }
 
 int bk_precond::apply_pw_chain(const double* x, const bk::DctFuse& d, int s, const double* cx, double ct, double* const* outs) {
-    for (int i = 0; i < s; ++i) BK_TRY(apply_pw(i == 0 ? x : outs[i - 1], d, cx[i], ct, outs[i]));
+    bk::DctFuse d1 = d;                      // (the scaled source belongs to the first link)
+    d1.src = nullptr;
+    for (int i = 0; i < s; ++i) BK_TRY(apply_pw(i == 0 ? x : outs[i - 1], i == 0 ? d : d1, cx[i], ct, outs[i]));
     return 0;
 }
 

@@ -21,6 +21,7 @@
 #include "dense.h"
 #include "ops.h"
 #include "sstep.h"
+#include "stream.h"
 
 namespace bk {
 
@@ -413,6 +414,9 @@ int gmres_core(bk_ctx* ctx, bk_op* A, const double* b, const double* bt, double*
     const bool block_log = ctx->opt("gmres_block_log", 0.0) != 0.0;
     const bool defer_update = ctx->opt("gmres_defer_update", 1.0) != 0.0;
     const bool orth_probe = ctx->opt("orth_probe", 0.0) != 0.0;
+    // cycle start (option gmres_fuse_v0): V[0] = r / beta written by the first operator application of the cycle instead of a pass of
+    // its own -- block cycles of unbordered operators only (the blocks' chained applications are what the fused pass belongs to)
+    const bool fuse_v0 = sstep_on && nt == 0 && ctx->opt("gmres_fuse_v0", 1.0) != 0.0;
     if (block_log) ctx->block_log_solves += 1;
     double beta_prev = 0.0, beta_now = 0.0, tol_now = 0.0;
     double* d_coef = nullptr;
@@ -581,7 +585,10 @@ int gmres_core(bk_ctx* ctx, bk_op* A, const double* b, const double* bt, double*
     if (trace) { ctx->hist_solves += 1; ctx->hist.push_back(-(double)ctx->hist_solves); ctx->hist.push_back(beta); }
 
     auto start_cycle = [&]() -> int {        // V[0] = r / beta ; first Arnoldi column
-        BK_TRY(v_axpbyz(ctx, n, 1.0 / beta, rsrc, 0.0, nullptr, B.vec(0)));
+        // (fuse_v0: the operator writes V[0] in the first transform pass of the application next_column(0) starts with -- bk_op::arm_v0;
+        // the same product per element, one read stream and one launch fewer)
+        if (!(fuse_v0 && aligned16(rsrc) && rsrc != B.vec(0) && A->arm_v0(rsrc, 1.0 / beta, B.vec(0))))
+            BK_TRY(v_axpbyz(ctx, n, 1.0 / beta, rsrc, 0.0, nullptr, B.vec(0)));
         rsrc = r;
         for (int q = 0; q < nt; ++q) B.tail(0)[q] = rt[q] / beta;
         B.dlt = 0.0;                           // a single vector is orthonormal
@@ -593,7 +600,8 @@ int gmres_core(bk_ctx* ctx, bk_op* A, const double* b, const double* bt, double*
         q_count = 0;                           // a new cycle: nothing speculative carries over
         pend.active = false;                   // (a deferred update of the finished cycle is void with its basis)
         beta_prev = 0.0; beta_now = beta; tol_now = tol;
-        BK_TRY(next_column(0, h.data(), &hnext));
+        const int e0 = next_column(0, h.data(), &hnext);
+        if (e0 != 0) { A->disarm_v0(); return e0; }      // (an armed V[0] does not outlive a failed cycle start)
         numops += 1;
         return 0;
     };
@@ -815,10 +823,12 @@ struct ShiftPrecOp : bk_op {
                 tmode = P->pw_fused_ok(u, u, u);
             }
         }
+        pw.src = nullptr;                     // (nothing armed carries over into a solve: arm_v0)
         mono_first = ctx->opt("gmres_monomial_shift", kMonomialShiftDefault) != 0.0;
         chain = ctx->opt("dct_x_turnaround", 1.0) != 0.0;
         // (options, the communicator and the plan only: every rank takes the same decision)
         spectral_check = ctx->opt("gmres_check_spectral", kCheckSpectralDefault) != 0.0 && P && !Pr && ctx->nranks == 1 && P->nrm2_spectral_ok();
+        check_nostore = ctx->opt("gmres_check_nostore", 1.0) != 0.0;
         if (!tmode) return 0;
         // g(u) = l + 2 nu u - 3 u^2 (examples/SH3d.jl:50-53); factor = c0 + cg g = A + u (B + C u)
         const double cg = order == 0 ? 1.0 : a1, c0 = order == 0 ? pl_shift : a0 + a1 * pl_shift;
@@ -835,11 +845,32 @@ struct ShiftPrecOp : bk_op {
     bool mono_first = false;      // option gmres_monomial_shift, read once per solve (init_fold)
     bool chain = true;            // option dct_x_turnaround, read once per solve (init_fold)
     bool spectral_check = false;  // option gmres_check_spectral and what the preconditioner's plan allows, once per solve (init_fold)
+    bool check_nostore = true;    // option gmres_check_nostore, once per solve (init_fold): the check's x-forward pass stores the spectrum only
     const double* rhs = nullptr;  // the solve's UNpreconditioned right-hand side (linsolve): b = Pl^-1 rhs
+    // GMRES cycle start (bk_op::arm_v0): in stencil-free mode on a single rank the next application's first transform pass can
+    // write V[0] = scale * src itself (DctFuse::src); the preconditioner decides per call whether that pass runs fused and writes
+    // V[0] in a pass of its own where it does not (bk_precond::pw_src_first)
+    void disarm_v0() override { pw.src = nullptr; }
+    bool arm_v0(const double* src, double scale, double* dst) override {
+        if (!tmode || ctx->nranks != 1 || src == dst || !P->pw_fused_ok(src, pw.u, dst)) return false;
+        pw.src = src; pw.src_scale = scale; pw.src_store = dst;
+        return true;
+    }
+    // the armed source, for one application of x (cleared); an application of anything but the armed vector: its scale pass first
+    int take_v0(const double* x, DctFuse* d) {
+        *d = pw;
+        pw.src = nullptr;
+        if (d->src && x != d->src_store) BK_TRY(P->pw_src_first(*d));
+        return 0;
+    }
     int apply(const double* x, const double*, double b0, double b1, double* out, double*) override {
         // out = b0 x + b1 * W(x)
         tmp_valid = false;
-        if (tmode) return P->apply_pw(x, pw, b0, b1, out);      // W = T (T'): see above
+        if (tmode) {                                            // W = T (T'): see above
+            DctFuse d;
+            BK_TRY(take_v0(x, &d));
+            return P->apply_pw(x, d, b0, b1, out);
+        }
         return apply_chain(x, b0, b1, out);
     }
     // a Newton-basis block in stencil-free mode: the s applications as ONE preconditioner chain (bk_precond::apply_pw_chain), which
@@ -848,7 +879,9 @@ struct ShiftPrecOp : bk_op {
         if (!tmode || !chain || s > sstep::kS) return bk_op::apply_block(x, s, b0, b1, theta, outs);
         double cx[sstep::kS];
         for (int i = 0; i < s; ++i) cx[i] = b0 - (theta ? theta[i] : 0.0);
-        return P->apply_pw_chain(x, pw, s, cx, b1, outs);
+        DctFuse d;
+        BK_TRY(take_v0(x, &d));
+        return P->apply_pw_chain(x, d, s, cx, b1, outs);
     }
     int apply_check(const double* x, const double*, double c0, double c1, double* out, double*) override {
         tmp_valid = false;
@@ -898,7 +931,7 @@ struct ShiftPrecOp : bk_op {
             BK_TRY(J->apply(x, nullptr, a0, a1, tmp, nullptr));
             c = -b1;
         }
-        BK_TRY(P->apply_nrm2(rhs_, c, tmp, nrm));
+        BK_TRY(P->apply_nrm2(rhs_, c, tmp, nrm, !check_nostore));
         tmp_valid = true;
         *done = 1;
         return 0;
@@ -1347,10 +1380,75 @@ struct BorderingState {          // caches dx = (shift + J)^-1 dR between BEC pa
     int cv_dx = 1;
 };
 
+namespace {
+
+// The bordered tail and the Newton update as ONE pass (option palc_fuse_update): t = a dx + x1, then x = x - t, element by element
+// what the two v_axpby calls  x1 <- a dx + 1 x1  and  x <- -1 x1 + 1 x  compute (their products by +-1 are exact) -- the product and
+// the two sums rounded on their own, a zero a skips the dx term as v_axpbyz skips an operand (0.0 + x1) -- without the store and the
+// reload of x1: three read streams and one write instead of 2 x (2 + 1).  x is read and written in place (no __restrict__ on it); dx
+// and x1 are only read and must not alias x.
+template <int VEC, bool NTH>
+__global__ void __launch_bounds__(kThreads) palc_update_kernel(size_t n, double a, const double* __restrict__ dx,
+                                                               const double* __restrict__ x1, double* x, int has_dx) {
+    auto one = [&](double d, double v, double xv) {
+        double t = 0.0;
+        if (has_dx) t = __dmul_rn(a, d);
+        t = __dadd_rn(t, v);
+        return __dadd_rn(-t, xv);
+    };
+    if (VEC == 2) {
+        stream_loop<4>(n >> 1, [&](auto uc, size_t i0, size_t st) {
+            constexpr int UU = decltype(uc)::value;
+            double2 dv[UU], vv[UU], xv[UU];
+#pragma unroll
+            for (int u = 0; u < UU; ++u) {
+                dv[u] = ld2<NTH>(dx, i0 + u * st);
+                vv[u] = ld2<NTH>(x1, i0 + u * st);
+                xv[u] = ld2<NTH>(x, i0 + u * st);
+            }
+#pragma unroll
+            for (int u = 0; u < UU; ++u) {
+                const double rx = one(dv[u].x, vv[u].x, xv[u].x), ry = one(dv[u].y, vv[u].y, xv[u].y);
+                if (NTH) {
+                    nt_d2 r; r.x = rx; r.y = ry;
+                    __builtin_nontemporal_store(r, reinterpret_cast<nt_d2*>(x) + (i0 + u * st));
+                } else {
+                    reinterpret_cast<double2*>(x)[i0 + u * st] = make_double2(rx, ry);
+                }
+            }
+        });
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = one(dx[n - 1], x1[n - 1], x[n - 1]);
+    } else {
+        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) x[i] = one(dx[i], x1[i], x[i]);
+    }
+}
+
+}  // namespace
+
+// x <- x - (x1 - dl dx): the launches v_axpby(-dl, dx, 1, x1) and v_axpby(-1, x1, 1, x) as one (x1 is left as it is)
+int palc_update(bk_ctx* ctx, size_t n, double dl, const double* dx, const double* x1, double* x) {
+    if (n == 0) return 0;
+    ProfScope ps(ctx, "blas1", 32.0 * n);
+    const bool vec = aligned16(dx) && aligned16(x1) && aligned16(x);
+    const int grid = grid_for(n, vec ? 2 : 1, 4096);
+    const double a = -dl;
+    const int has_dx = a != 0.0 ? 1 : 0;
+    if (vec && nt_hint(ctx, n))
+        hipLaunchKernelGGL((palc_update_kernel<2, true>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, x, has_dx);
+    else if (vec)
+        hipLaunchKernelGGL((palc_update_kernel<2, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, x, has_dx);
+    else
+        hipLaunchKernelGGL((palc_update_kernel<1, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, x, has_dx);
+    BK_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 // BEC, src/LinearBorderSolver.jl:125-144.  x1 <- (shift+J)^-1 R - dl * dx.
+// xnew != NULL (bk_newton_palc, option palc_fuse_update): the tail pass is palc_update, xnew <- xnew - (x1 - dl dx), and x1 is left
+// holding (shift+J)^-1 R WITHOUT the dl term -- only for callers that do not read x1 afterwards.
 static int bec(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R, double nn,
                double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_gmres_opts& ls,
-               bk_precond* pl, BorderingState& st, double* x1, double* dl, int* cv, int it[2]) {
+               bk_precond* pl, BorderingState& st, double* x1, double* dl, int* cv, int it[2], double* xnew = nullptr) {
     const size_t n = J->n;
     GmresResult r1;
     const double a0 = has_shift ? shift : 0.0;
@@ -1365,7 +1463,8 @@ static int bec(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, doubl
     BK_TRY(v_dot2(ctx, n, dzu, x1, st.dx, d));
     d[0] *= dotscale; d[1] *= dotscale;
     *dl = (nn - d[0] * xiu) / (dzp * xip - d[1] * xiu);
-    BK_TRY(v_axpby(ctx, n, -(*dl), st.dx, 1.0, x1));
+    if (xnew) BK_TRY(palc_update(ctx, n, *dl, st.dx, x1, xnew));
+    else BK_TRY(v_axpby(ctx, n, -(*dl), st.dx, 1.0, x1));
     *cv = r1.converged & st.cv_dx;
     it[0] = r1.niter; it[1] = st.it_dx;
     return 0;
@@ -1373,13 +1472,17 @@ static int bec(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, doubl
 
 int bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R, double nn,
                   double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_bordering_opts& bo,
-                  const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2]) {
+                  const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2],
+                  double* xnew) {
+    // xnew (optional; needs check_precision off): the Newton update xnew <- xnew - dX rides in the tail pass of the one BEC pass, and
+    // dX is left holding x1 = (shift+J)^-1 R without the dl term (see bec)
+    if (xnew && bo.check_precision) return set_error(ctx, "bls_bordering: the fused update needs check_precision off");
     const size_t n = J->n;
     WsGuard ws(ctx);
     BorderingState st;
     BK_TRY(ws.get(n, &st.dx));
     int cv = 0, it[2] = {0, 0};
-    BK_TRY(bec(ctx, J, dR, dzu, dzp, R, nn, xiu, xip, has_shift, shift, dotscale, ls, pl, st, dX, dl, &cv, it));
+    BK_TRY(bec(ctx, J, dR, dzu, dzp, R, nn, xiu, xip, has_shift, shift, dotscale, ls, pl, st, dX, dl, &cv, it, xnew));
     int k = 0;
     bool fail = true;
     double *dXr = nullptr, *dX1 = nullptr;
@@ -1464,6 +1567,12 @@ int bk_bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu,
     if (bopts->k < 1) return set_error(ctx, "BorderingBLS: number of recursions must be positive");
     return bls_bordering(ctx, J, dR, dzu, dzp, R, n, xiu, xip, has_shift != 0, shift, dotscale, *bopts, *lsopts, pl, dX,
                          dl, converged, itlinear);
+}
+
+int bk_palc_update(bk_ctx* ctx, size_t n, double dl, const double* dx, const double* x1, double* x) {
+    if (!ctx || !dx || !x1 || !x) return -1;
+    if (x == dx || x == x1) return set_error(ctx, "bk_palc_update: x must not alias dx or x1");
+    return palc_update(ctx, n, dl, dx, x1, x);
 }
 
 int bk_bls_matrixfree(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R,
@@ -1658,6 +1767,9 @@ int bk_newton_palc(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
     int step = 0, itlin = 0;
     res->residuals[0] = r;
     bool line_step = true;
+    // option palc_fuse_update (read once per corrector call): BorderingBLS without check_precision and no line search -- nobody reads
+    // u after the update, so x <- x - u rides in the tail pass of the bordering solve (bls_bordering: xnew)
+    const bool fuse_update = bo->kind == 0 && bo->check_precision == 0 && !linesearch && ctx->opt("palc_fuse_update", 1.0) != 0.0;
     int compute = newton_cb(no, x, res_f, r, 0, 0, pc, z0u, z0p, 0);                // Palc.jl:235
     while (step < no->max_iterations && r > no->tol && line_step && compute) {
         par[ipar] = pc;                                    // dFdp = (F(x, p + eps) - res_f)/eps, Palc.jl:239-240
@@ -1673,7 +1785,7 @@ int bk_newton_palc(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
             it[0] = itm; it[1] = 0;
         } else {
             s = bls_bordering(ctx, J, dFdp, tauu, taup, res_f, res_n, theta, 1.0 - theta, false, 0.0, dotscale, *bo,
-                              *lsopts, pl, u, &up, &cv, it);
+                              *lsopts, pl, u, &up, &cv, it, fuse_update ? x : nullptr);
         }
         bk_op_destroy(J);
         if (s != 0) return s;
@@ -1700,7 +1812,7 @@ int bk_newton_palc(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
             alpha = alpha0;                                  // "we put back the initial value"
             par[ipar] = pc;
         } else {
-            BK_TRY(v_axpby(ctx, n, -1.0, u, 1.0, x));        // x = minus!!(x, u), Palc.jl:282
+            if (!fuse_update) BK_TRY(v_axpby(ctx, n, -1.0, u, 1.0, x));        // x = minus!!(x, u), Palc.jl:282
             pc = std::min(std::max(pc - up, p_min), p_max);  // clamp, :283
             par[ipar] = pc;
             BK_TRY(bk_residual(prob, x, par, nparams, res_f));

@@ -610,6 +610,13 @@ class BorderedArray:
         return len(self.u) + 1
 
 
+def palc_update(x, x1, dx, dl):
+    """x <- x - (x1 - dl dx) in one pass (bk_palc_update): what newton_palc_native runs instead of the bordered tail and the Newton
+    update when nobody reads x1 afterwards (option palc_fuse_update).  Same bits as x1.add_(dx, -dl, 1.0); x.add_(x1, -1.0, 1.0)."""
+    x.ctx.check(x.ctx.lib.bk_palc_update(x.ctx.h, x.n, float(dl), _ptr(dx.t), _ptr(x1.t), _ptr(x.t)), "bk_palc_update")
+    return x
+
+
 @dataclass
 class BorderingBLS:
     """src/LinearBorderSolver.jl:59-79.  With a native GMRES ``solver`` and HipVec arguments the whole bordered

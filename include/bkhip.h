@@ -289,6 +289,11 @@ int bk_bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu,
  * the passes, so this implementation solves it once and reports that solve's count and flag for every pass -- the same
  * numbers the repeated (deterministic) solve would return, at one solve less per pass; itlinear[0] is the last pass's
  * solve with the refreshed right-hand side, as in the reference.                                                      */
+/* Probe of the pass bk_newton_palc runs instead of the bordered tail x1 <- x1 - dl dx and the Newton update x <- x - x1 when
+ * nobody reads x1 afterwards (BorderingBLS without check_precision, no line search; context option "palc_fuse_update",
+ * default 1): x <- x - (x1 - dl dx) in ONE pass over dx, x1 and x, rounded exactly as bk_vec_axpby(-dl, dx, 1, x1) followed by
+ * bk_vec_axpby(-1, x1, 1, x).  x1 and dx are only read; x must not alias them.                                         */
+int bk_palc_update(bk_ctx* ctx, size_t n, double dl, const double* dx, const double* x1, double* x);
 int bk_bls_matrixfree(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp,
                       const double* R, double n, double xiu, double xip, int has_shift,
                       double shift, double dotscale, const bk_gmres_opts* lsopts, double* dX,

@@ -419,6 +419,13 @@ function (lbs::HipBorderingBLS)(J::HipJacobian, dR::HipVec, dzu::HipVec, dzp::T,
     return dX, dl[], cv[] == 1, (Int(it[1]), Int(it[2]))
 end
 
+# x <- x - (x1 - dl dx) in one pass: the bordered tail and the Newton update of the native corrector (option palc_fuse_update)
+function palc_update!(x::HipVec, x1::HipVec, dx::HipVec, dl::Real)
+    check(x.ctx, ccall((:bk_palc_update, libbkhip[]), Cint, (Ptr{Cvoid}, Csize_t, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+                       x.ctx.h, x.n, dl, dx.p, x1.p, x.p), "bk_palc_update")
+    return x
+end
+
 # bls(J, a, b, 0, 0, 1; shift = Complex(0, -ω)) of src/codim2/MinAugHopf.jl:17, 72-76: complex border, one BEC pass
 function (lbs::HipBorderingBLS)(J::HipJacobian, dR::HipCVec, dzu::HipCVec, dzp, R::HipCVec, n, ξu = 1.0, ξp = 1.0;
                                 shift = nothing, dotp = nothing, applyξu! = nothing)

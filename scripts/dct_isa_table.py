@@ -23,7 +23,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "bifurcationkit.jl_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-ffp-contract=off"]
-PARAMS = ["NT", "MODE", "AX0", "NTM", "DOT", "FZ", "SLAB", "FZS", "TURN", "CN", "NRM"]
+PARAMS = ["NT", "MODE", "AX0", "NTM", "DOT", "FZ", "SLAB", "FZS", "TURN", "CN", "NRM", "SRC"]
 CN = PARAMS.index("CN")
 
 
@@ -74,7 +74,7 @@ def stats(k):
 def label(args):
     a = dict(zip(PARAMS, args))
     s = "<%d,%d,%s" % (a["NT"], a["MODE"], "AX0" if a["AX0"] else ("z" if a["MODE"] == 2 else "y"))
-    for f in ("NTM", "DOT", "FZ", "FZS", "TURN", "NRM"):
+    for f in ("NTM", "DOT", "FZ", "FZS", "TURN", "NRM", "SRC"):
         if a[f]:
             s += "," + f
     if a["SLAB"]:
