@@ -158,6 +158,11 @@ SIGNATURES = {
                                    C.POINTER(GmresOpts), VP, VP, c_double_p, c_int_p, c_int_p]),
     "bk_bls_block_matrixfree": (I, [VP, VP, I, C.POINTER(VP), C.POINTER(VP), c_double_p, VP, c_double_p, I, D, D,
                                     C.POINTER(GmresOpts), VP, c_double_p, c_int_p, c_int_p]),
+    "bk_bls_matrixfree_pl": (I, [VP, VP, VP, VP, D, VP, D, D, D, I, D, D, C.POINTER(GmresOpts), VP, VP, c_double_p,
+                                 c_int_p, c_int_p]),
+    "bk_bls_block_matrixfree_pl": (I, [VP, VP, I, C.POINTER(VP), C.POINTER(VP), c_double_p, VP, c_double_p, I, D, D,
+                                       C.POINTER(GmresOpts), VP, VP, c_double_p, c_int_p, c_int_p]),
+    "bk_bordered_tail": (I, [VP, SZ, I, VP, VP, C.POINTER(VP), C.POINTER(VP), c_double_p, c_double_p]),
     "bk_gmres_cshift": (I, [VP, VP, VP, VP, VP, VP, D, D, D, C.POINTER(GmresOpts), VP, c_int_p, c_int_p, c_double_p]),
     "bk_bls_bordering_cshift": (I, [VP, VP, VP, VP, VP, VP, D, D, VP, VP, D, D, D, D, D, D, D, C.POINTER(GmresOpts),
                                     VP, VP, VP, c_double_p, c_int_p, c_int_p]),
@@ -183,6 +188,7 @@ SIGNATURES = {
     "bk_d2f": (I, [VP, VP, c_double_p, I, VP, VP, VP]),
     "bk_djdp": (I, [VP, VP, c_double_p, I, I, VP, VP]),
     "bk_fold_contract": (I, [VP, VP, c_double_p, I, I, VP, VP, I, C.POINTER(VP), c_double_p]),
+    "bk_fold_border": (I, [VP, VP, c_double_p, I, I, VP, VP, VP, c_double_p]),
     "bk_fold_terms": (I, [VP, VP, VP, c_double_p, I, I, VP, VP, C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP, VP, VP,
                           c_double_p, c_double_p, c_int_p, c_int_p]),
     "bk_fold_linsolve": (I, [VP, VP, VP, c_double_p, I, I, VP, VP, I, C.POINTER(VP), c_double_p, C.POINTER(GmresOpts), VP,

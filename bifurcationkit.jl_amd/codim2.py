@@ -15,6 +15,9 @@ path (the reference assembles the systems for MatrixBLS / MinAugMatrixBased, whi
 Problems: SwiftHohenberg (2-D / 3-D) and SwiftHohenberg1D -- symmetric, J' = J (:79-84).  sigma_p, dpF and sigma_x are analytic
 (the Jacobians depend on the parameters only through their pointwise term), where the reference takes central differences.
 The bordered vectors v, w of a point are solved once and serve both its residual and its Newton step.
+With ``bls = MatrixFreeBLS(ls, use_pl=True)`` the fold entries run the branch without `usehessian` (:54-69, :136-145) on the
+preconditioned bordered solver: [J a; b' 0] for (v, sigma) and w, [J dpF; sigma_x' sigma_p] per Newton step -- systems that stay
+regular at the fold, where J \\ a and J \\ F do not converge (context option fold_bordered).
 
 Codim-2 points: on Hopf curves generalised Hopf (Bautin) points are detected, bisected and given their normal form
 (continuation_hopf(..., detect_codim2 = 1 | 2), get_normal_form on a "gh" point); Bogdanov-Takens, zero-Hopf and Hopf-Hopf points
@@ -34,7 +37,7 @@ import torch
 
 from . import _lib as L
 from . import continuation as Cn
-from .hip import BorderedArray, BorderingBLS, HipVec, _GMRES, _ptr, newton_opts
+from .hip import BorderedArray, BorderingBLS, HipVec, MatrixFreeBLS, _GMRES, _ptr, newton_opts
 
 
 def _nanmax(*vals):
@@ -106,8 +109,53 @@ def dpF(prob, x: HipVec, pars, ipar: int) -> HipVec:
     return _into_similar(prob, "bk_residual_dparam", x, pv, int(ipar), 1.0)
 
 
-def _bls_opts(bls: BorderingBLS):
+def _bls_opts(bls):
+    if isinstance(bls, MatrixFreeBLS):          # the entry points take the struct; with fold_bordered = 1 they do not read it
+        return L.BorderingOpts(1e-12, 0, 1, 1)
     return L.BorderingOpts(bls.tol, 1 if bls.check_precision else 0, bls.k, 0)
+
+
+def _bordered_path(bls) -> bool:
+    """True when ``bls`` selects the fold formulation on the system that is regular at the fold (context option fold_bordered):
+    MatrixFreeBLS(ls, use_pl=True), every solve ONE GMRES on [J a; b' c] left-preconditioned by diag(Pl, 1)."""
+    if isinstance(bls, MatrixFreeBLS):
+        if not bls.use_pl:
+            raise TypeError("the fold formulation takes BorderingBLS or MatrixFreeBLS(ls, use_pl=True)")
+        return True
+    return False
+
+
+class _fold_bordered:
+    """Context option fold_bordered set to 1 around a native call and put back afterwards (the library reads it once per call).
+    With ``on`` false nothing is touched.  An option cannot be unset: on a context that never had it, it is left at 0, which the
+    library reads as the default path (tests/test_gpu_fold_bordered.py: unset and 0 give the same bits)."""
+
+    def __init__(self, ctx, on: bool):
+        self.ctx, self.on = ctx, bool(on)
+        self.prev = None
+
+    def __enter__(self):
+        if self.on:
+            try:
+                self.prev = self.ctx.get_option("fold_bordered")
+            except L.BkHipError:
+                self.prev = 0.0
+            self.ctx.set_option("fold_bordered", 1.0)
+        return self
+
+    def __exit__(self, *exc):
+        if self.on:
+            self.ctx.set_option("fold_bordered", self.prev)
+        return False
+
+
+def fold_border(prob, x: HipVec, pars, ipar: int, v: HipVec, w: HipVec):
+    """(sigx, sigma_p) of bk_fold_border: sigx = -w h(x) v as a vector, <sigx, X> = -<w, d2F(x)[v, X]>; sigma_p = -<w, dJ/dp v>."""
+    ctx, out = prob.ctx, x.similar()
+    sp = C.c_double()
+    ctx.check(ctx.lib.bk_fold_border(prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), _ptr(v.t), _ptr(w.t), _ptr(out.t),
+                                     C.byref(sp)), "bk_fold_border")
+    return out, sp.value
 
 
 def _solve2(ls: _GMRES, J, rhs1: HipVec, rhs2: HipVec):
@@ -333,13 +381,18 @@ def start_vector_eigen(prob, x: HipVec, p: float, eig):
 
 
 # ------------------------------------------------------------------------------------------ newton_fold
-def newton_fold(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS | None = None, tol=1e-12,
-                max_iterations=25, norm_inf=False):
+def newton_fold(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS | MatrixFreeBLS | None = None,
+                tol=1e-12, max_iterations=25, norm_inf=False):
     """newton_fold (:211-233) with FoldLinearSolverMinAug under _newton (src/Newton.jl:66-114), call by call on the plugin
     surface: the residual (:16-38) solves bls(J, a, b, 0, 0, 1) for (v, sigma) and bls(J', b, a, 0, 0, 1) for w (no second
     solve when ``a is b``: J' = J); each Newton step is foldMALinearSolver's usehessian branch (:146-164) with ls(J, F, dpF),
-    d2F + inner for sigma_x and dJ/dp v + inner for sigma_p.  v, w of a point serve its residual and its step."""
+    d2F + inner for sigma_x and dJ/dp v + inner for sigma_p.  v, w of a point serve its residual and its step.
+
+    ``bls = MatrixFreeBLS(ls, use_pl=True)``: the same two calls of the residual go to the preconditioned bordered solver, and each
+    Newton step is the branch without ``usehessian`` (:136-145): sigma_x as a vector (fold_border) and ONE solve
+    bls(J, dpF, sigma_x, sigma_p, F, sigma) -- regular at the fold, where J \\ F is not."""
     bls = bls if bls is not None else BorderingBLS(ls, check_precision=False)
+    bordered = _bordered_path(bls)
     ipar = prob.ipar
     x, p = x0.copy(), float(p0)
     itlin, bad = 0, 0
@@ -364,6 +417,14 @@ def newton_fold(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _GMRES, b
         nonlocal p, itlin, bad
         pars = prob._pvec(p)
         J = prob.jacobian(x, p)
+        if bordered:
+            sigx, sp = fold_border(prob, x, pars, ipar, v, w)
+            dX, dsig, cv, it = bls(J, dpF(prob, x, pars, ipar), sigx, sp, F, sigma)
+            itlin += int(it)
+            bad += 0 if cv else 1
+            x.add_(dX, -1.0)
+            p -= dsig
+            return
         x1, x2, cv, it = _solve2(ls, J, F, dpF(prob, x, pars, ipar))
         itlin += int(np.sum(it))
         bad += 0 if cv else 1
@@ -381,9 +442,10 @@ def newton_fold(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _GMRES, b
                 w=w.copy() if w is v else w, sigma=sigma, unconverged_solves=bad)
 
 
-def newton_fold_native(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS | None = None,
-                       tol=1e-12, max_iterations=25, norm_inf=False, callback=None):
-    """The same as one library call (bk_newton_fold)."""
+def newton_fold_native(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _GMRES,
+                       bls: BorderingBLS | MatrixFreeBLS | None = None, tol=1e-12, max_iterations=25, norm_inf=False, callback=None):
+    """The same as one library call (bk_newton_fold); with ``bls = MatrixFreeBLS(ls, use_pl=True)`` under the context option
+    fold_bordered = 1, set and put back around the call."""
     bls = bls if bls is not None else BorderingBLS(ls, check_precision=False)
     ctx = prob.ctx
     x = x0.copy()
@@ -395,26 +457,29 @@ def newton_fold_native(prob, x0: HipVec, p0: float, a: HipVec, b: HipVec, ls: _G
     bo, lo = _bls_opts(bls), ls._opts()
     res = L.NewtonResult()
     bad0 = ctx.get_option("fold_unconverged_solves")
-    ctx.check(ctx.lib.bk_newton_fold(ctx.h, prob.h, _ptr(x.t), C.byref(p), _carr(pv), len(pv), prob.ipar, _ptr(a.t), _ptr(b.t),
-                                     C.byref(no), C.byref(bo), C.byref(lo), ls._pl(), _ptr(v.t), _ptr(w.t), C.byref(sigma),
-                                     C.byref(res)), "bk_newton_fold")
+    with _fold_bordered(ctx, _bordered_path(bls)):
+        ctx.check(ctx.lib.bk_newton_fold(ctx.h, prob.h, _ptr(x.t), C.byref(p), _carr(pv), len(pv), prob.ipar, _ptr(a.t), _ptr(b.t),
+                                         C.byref(no), C.byref(bo), C.byref(lo), ls._pl(), _ptr(v.t), _ptr(w.t), C.byref(sigma),
+                                         C.byref(res)), "bk_newton_fold")
     return dict(u=BorderedArray(x, p.value), converged=bool(res.converged), itnewton=res.itnewton, itlineartot=res.itlinear,
                 residuals=[res.residuals[i] for i in range(res.itnewton + 1)], v=v, w=w, sigma=sigma.value,
                 unconverged_solves=int(ctx.get_option("fold_unconverged_solves") - bad0))
 
 
 # ------------------------------------------------------------------------------------------ the fold problem G(X, p2)
-def fold_terms(prob, x: HipVec, pars, ipar: int, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS):
-    """bk_fold_terms: (v, w, sigma, converged, (itv, itw)); w is v itself when ``a is b`` (J' = J: no second solve)."""
+def fold_terms(prob, x: HipVec, pars, ipar: int, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS | MatrixFreeBLS):
+    """bk_fold_terms: (v, w, sigma, converged, (itv, itw)); w is v itself when ``a is b`` (J' = J: no second solve).  With
+    ``bls = MatrixFreeBLS(ls, use_pl=True)`` each of (v, sigma) and w is ONE preconditioned bordered solve (option fold_bordered)."""
     ctx = prob.ctx
     v = x.similar()
     w = v if a is b else x.similar()
     sigma, cv = C.c_double(), C.c_int()
     it = (C.c_int * 2)()
     bo, lo = _bls_opts(bls), ls._opts()
-    ctx.check(ctx.lib.bk_fold_terms(ctx.h, prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), _ptr(a.t), _ptr(b.t),
-                                    C.byref(bo), C.byref(lo), ls._pl(), _ptr(v.t), _ptr(w.t), C.byref(sigma), None, C.byref(cv),
-                                    it), "bk_fold_terms")
+    with _fold_bordered(ctx, _bordered_path(bls)):
+        ctx.check(ctx.lib.bk_fold_terms(ctx.h, prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), _ptr(a.t), _ptr(b.t),
+                                        C.byref(bo), C.byref(lo), ls._pl(), _ptr(v.t), _ptr(w.t), C.byref(sigma), None, C.byref(cv),
+                                        it), "bk_fold_terms")
     return v, w, sigma.value, bool(cv.value), (it[0], it[1])
 
 
@@ -422,9 +487,10 @@ class FoldProblem(_MinAugProblem):
     """FoldMinimallyAugmentedFormulation(prob, a, b, ...) + FoldMAProblem with lens2 (src/codim2/MinAugFold.jl,
     continuation_fold :407-453): unknown X = BorderedArray(x, p1), the bordered vectors from bk_fold_terms."""
 
-    def __init__(self, prob, lens2: str, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS | None = None):
+    def __init__(self, prob, lens2: str, a: HipVec, b: HipVec, ls: _GMRES, bls: BorderingBLS | MatrixFreeBLS | None = None):
         super().__init__(prob, lens2, a, b, ls)
         self.bls = bls if bls is not None else BorderingBLS(ls, check_precision=False)
+        self.bordered = _bordered_path(self.bls)     # MatrixFreeBLS(ls, use_pl=True): bordered vectors AND linear solver on that path
 
     _p1 = staticmethod(lambda X: X.p)
     _vec = staticmethod(BorderedArray)
@@ -450,7 +516,9 @@ class FoldProblem(_MinAugProblem):
 
 
 class FoldLinearSolverMinAug(_MinAugLinearSolver):
-    """FoldLinearSolverMinAug (:168-178) -> foldMALinearSolver, usehessian branch (:146-164) as bk_fold_linsolve."""
+    """FoldLinearSolverMinAug (:168-178) -> foldMALinearSolver as bk_fold_linsolve: the usehessian branch (:146-164), or -- for a
+    FoldProblem built with MatrixFreeBLS(ls, use_pl=True) -- the full system [J dpF; sigma_x' sigma_p] (:136-145), one
+    preconditioned bordered solve per right-hand side (option fold_bordered)."""
 
     def _run(self, J: _JacobianMinAug, rhs):
         F, v, w, arr, npar, dX, ru, dxp = _linsolve_args(J, rhs)
@@ -459,8 +527,9 @@ class FoldLinearSolverMinAug(_MinAugLinearSolver):
         ds = (C.c_double * m)()
         cv, it = C.c_int(), C.c_int()
         lo = F.ls._opts()
-        ctx.check(ctx.lib.bk_fold_linsolve(ctx.h, F.prob.h, _ptr(J.X.u.t), arr, npar, F.ipar1, _ptr(v.t), _ptr(w.t), m, ru, rp,
-                                           C.byref(lo), F.ls._pl(), dxp, ds, C.byref(cv), C.byref(it)), "bk_fold_linsolve")
+        with _fold_bordered(ctx, getattr(F, "bordered", False)):
+            ctx.check(ctx.lib.bk_fold_linsolve(ctx.h, F.prob.h, _ptr(J.X.u.t), arr, npar, F.ipar1, _ptr(v.t), _ptr(w.t), m, ru, rp,
+                                               C.byref(lo), F.ls._pl(), dxp, ds, C.byref(cv), C.byref(it)), "bk_fold_linsolve")
         return [BorderedArray(dX[k], ds[k]) for k in range(m)], bool(cv.value), it.value
 
 
@@ -481,19 +550,22 @@ def _norminf_fold(z):
 
 def continuation_fold(prob, fold_guess: BorderedArray, p2: float, lens2: str, a: HipVec, b: HipVec, ls: _GMRES,
                       cp: Cn.ContinuationPar, theta=0.5, norm_inf=True, update_minaug_every_step=1, save_sol=False,
-                      ds_sequence=None, verbosity=0) -> FoldBranch:
+                      ds_sequence=None, verbosity=0, bls: BorderingBLS | MatrixFreeBLS | None = None) -> FoldBranch:
     """continuation_fold(prob, alg = PALC(tangent = Secant()), foldpointguess, par, lens1, lens2, a, b, options_cont) (:369-453):
     PALC on G(X, p2) through continuation.newton_palc with BorderingBLS(solver = FoldLinearSolverMinAug(), check_precision =
     false) (:445-453), Secant tangent only (the reference warns against Bordered on folds, :390-392), the two starting points of
     continuation (Continuation.jl:349-456) by newton on G, step-size control of continuation.py.  After every converged step a, b
     are updated (update_minaug_every_step = 1) and BT, CP recorded.  ``ds_sequence`` (optional) replaces the step-size control by
-    a fixed list of steps (comparisons with a restatement).  Codim-2 points are not located."""
+    a fixed list of steps (comparisons with a restatement).  Codim-2 points are not located.
+    ``bls`` (optional): the bordered solver of the formulation's OWN solves -- MatrixFreeBLS(ls, use_pl=True) runs the bordered
+    vectors and the fold linear solver on the preconditioned bordered system; the outer PALC solve stays BorderingBLS over the fold
+    linear solver, as in the reference (:449)."""
     br = FoldBranch()
 
     def record_x(X, bt, tau):
         br.p1.append(X.p); br.BT.append(bt); br.CP.append(tau.p)
 
-    _continuation_minaug(FoldProblem(prob, lens2, a, b, ls), FoldLinearSolverMinAug(), "fold", br, fold_guess, p2, cp, theta,
+    _continuation_minaug(FoldProblem(prob, lens2, a, b, ls, bls), FoldLinearSolverMinAug(), "fold", br, fold_guess, p2, cp, theta,
                          _norminf_fold if norm_inf else (lambda z: z.norm()), update_minaug_every_step, save_sol, ds_sequence,
                          verbosity, record_x, skipped=lambda X: float("nan"), describe=lambda X: f"p1={X.p:+.8f}")
     return br

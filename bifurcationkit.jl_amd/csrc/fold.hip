@@ -54,6 +54,25 @@ struct FoldContract {
     }
 };
 
+// sigma_x as a vector: sigx[i] = -((w[i] h(u[i])) v[i]), the border row of the full fold Jacobian (MinAugFold.jl:136-145), so that
+// <sigx, X> = -<w, d2F(u)[v, X]>.  Three read streams and one write.
+struct FoldBorder {
+    static constexpr int NIN = 3, NOUT = 1, U = 2, FIELDS = 1;
+    static constexpr bool JOINT = false;
+    const double* in[NIN];          // u, v, w
+    double* out[NOUT];              // sigx
+    FoldPoly P;
+    __device__ __forceinline__ void operator()(const double (&x)[NIN], double (&o)[NOUT]) const {
+        o[0] = -((x[2] * fold_poly(P.h, x[0])) * x[1]);
+    }
+};
+
+static int v_fold_border(bk_ctx* ctx, size_t n, const double* u, const double* v, const double* w, const double h[4], double* sigx) {
+    FoldBorder pass{{u, v, w}, {sigx}, {}};
+    for (int i = 0; i < 4; ++i) { pass.P.h[i] = h[i]; pass.P.g[i] = 0.0; }
+    return stream_write(ctx, "fold_border", n, pass);
+}
+
 static int v_fold_pw(bk_ctx* ctx, size_t n, const double* u, const double c[4], const double* x1, const double* x2, double* out) {
     if (n == 0) return 0;
     FoldPoly P{};
@@ -129,6 +148,62 @@ int fold_linsolve(bk_ctx* ctx, bk_problem* prob, bk_op* J, const double* x, cons
     return minaug_update(ctx, n, S, nrhs, dsig, 1, dX);
 }
 
+// Context option fold_bordered = 1: the same two functions on the system that is regular at the fold (MinAugFold.jl:54-69 and
+// :136-145 handed to MatrixFreeBLS with the left preconditioner diag(Pl, 1): minaug_bordered_solve -> bls_matrixfree_pl).
+// (v, sigma) from ONE solve of [J a; b' 0][v; sigma] = [0; 1]; w from the adjoint system, or w = v when a and b are the same vector.
+int fold_terms_bordered(bk_ctx* ctx, bk_op* J, size_t n, const double* a, const double* b, const bk_gmres_opts& lo, bk_precond* pl,
+                        double* zero, double* v, double* w, double* sigma, int* cv, int it[2]) {
+    BK_TRY(v_zero(ctx, n, zero));
+    const double c0 = 0.0, one = 1.0;
+    GmresResult r1, r2;
+    r2.converged = 1;
+    BK_TRY(minaug_bordered_solve(ctx, J, 1, &a, &b, &c0, zero, &one, lo, pl, v, sigma, &r1));
+    if (a == b) {
+        if (w != v) BK_TRY(v_copy(ctx, n, v, w));
+    } else {
+        double s2 = 0.0;
+        BK_TRY(minaug_bordered_solve(ctx, J, 1, &b, &a, &c0, zero, &one, lo, pl, w, &s2, &r2));
+    }
+    *cv = r1.converged & r2.converged;
+    it[0] = r1.niter;
+    it[1] = r2.niter;
+    return 0;
+}
+
+// [J dpF; sigx' sigma_p][dX_k; dsig_k] = [rhsu_k; rhsp_k]: sigx from the FoldBorder pass, sigma_p from FoldContract<0>, one bordered
+// solve per right-hand side, all sharing atil = Pl^-1 dpF
+int fold_linsolve_bordered(bk_ctx* ctx, bk_problem* prob, bk_op* J, const double* x, const double* params, int nparams, int ipar,
+                           const double* v, const double* w, int nrhs, const double* const* rhsu, const double* rhsp,
+                           const bk_gmres_opts& lo, bk_precond* pl, double* const* dX, double* dsig, int* cv, int* itlinear) {
+    const size_t n = prob->nloc;
+    if (!pl) return set_error(ctx, "fold: fold_bordered = 1 needs the left preconditioner");
+    double h[4], g[4];
+    BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
+    WsGuard ws(ctx);
+    double *dpF = nullptr, *atil = nullptr, *sigx = nullptr;
+    BK_TRY(ws.get(n, &dpF));
+    BK_TRY(ws.get(n, &atil));
+    BK_TRY(ws.get(n, &sigx));
+    BK_TRY(pde_dparam(ctx, prob->desc.pde, ipar, n, 1.0, x, dpF));                // analytic dpF (:88-89)
+    BK_TRY(pl->apply(dpF, atil));
+    BK_TRY(v_fold_border(ctx, n, x, v, w, h, sigx));
+    double t[1];
+    BK_TRY(v_fold_contract(ctx, n, x, v, w, 0, nullptr, h, g, t));
+    const double sp = -t[0];
+    const double* acol[1] = {dpF};
+    const double* atl[1] = {atil};
+    const double* brow[1] = {sigx};
+    *cv = 1;
+    *itlinear = 0;
+    for (int k = 0; k < nrhs; ++k) {
+        GmresResult r;
+        BK_TRY(minaug_bordered_solve(ctx, J, 1, acol, brow, &sp, rhsu[k], &rhsp[k], lo, pl, dX[k], &dsig[k], &r, atl));
+        *cv &= r.converged;
+        *itlinear += r.niter;
+    }
+    return 0;
+}
+
 }  // namespace
 }  // namespace bk
 
@@ -166,6 +241,21 @@ int bk_fold_contract(bk_problem* prob, const double* u, const double* params, in
     return 0;
 }
 
+int bk_fold_border(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* v, const double* w,
+                   double* sigx, double* sigma_p) {
+    if (!prob || !u || !params || !v || !w || !sigx) return -1;
+    double h[4], g[4];
+    BK_TRY(fold_polys(prob, params, nparams, ipar, h, g));
+    if (sigx == u || sigx == v || sigx == w) return set_error(prob->ctx, "bk_fold_border: sigx must not alias u, v or w");
+    BK_TRY(v_fold_border(prob->ctx, prob->nloc, u, v, w, h, sigx));
+    if (sigma_p) {
+        double t[1];
+        BK_TRY(v_fold_contract(prob->ctx, prob->nloc, u, v, w, 0, nullptr, h, g, t));
+        *sigma_p = -t[0];
+    }
+    return 0;
+}
+
 int bk_fold_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar,
                   const double* a, const double* b, const bk_bordering_opts* bopts, const bk_gmres_opts* lsopts,
                   bk_precond* pl, double* v, double* w, double* sigma, double* sigma_p, int* converged, int itlinear[2]) {
@@ -183,7 +273,8 @@ int bk_fold_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* 
     {
         JPair jp;
         BK_TRY(jp.make(prob, x, params, nparams));
-        BK_TRY(fold_terms(ctx, jp.J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it));
+        if (minaug_bordered(ctx)) BK_TRY(fold_terms_bordered(ctx, jp.J, n, a, b, *lsopts, pl, zero, v, w, sigma, &cv, it));
+        else BK_TRY(fold_terms(ctx, jp.J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it));
     }
     if (sigma_p) {
         double t[1];
@@ -205,7 +296,10 @@ int bk_fold_linsolve(bk_ctx* ctx, bk_problem* prob, const double* x, const doubl
     JPair jp;
     BK_TRY(jp.make(prob, x, params, nparams));
     int cv = 0, it = 0;
-    BK_TRY(fold_linsolve(ctx, prob, jp.J, x, params, nparams, ipar, v, w, nrhs, rhsu, rhsp, *lsopts, pl, dX, dsigma, &cv, &it));
+    if (minaug_bordered(ctx))
+        BK_TRY(fold_linsolve_bordered(ctx, prob, jp.J, x, params, nparams, ipar, v, w, nrhs, rhsu, rhsp, *lsopts, pl, dX, dsigma, &cv, &it));
+    else
+        BK_TRY(fold_linsolve(ctx, prob, jp.J, x, params, nparams, ipar, v, w, nrhs, rhsu, rhsp, *lsopts, pl, dX, dsigma, &cv, &it));
     if (converged) *converged = cv;
     if (itlinear) *itlinear = it;
     return 0;
@@ -232,6 +326,7 @@ int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
     double par[BK_MAX_PARAMS];
     for (int i = 0; i < nparams; ++i) par[i] = params[i];
     double pc = *p;
+    const bool bordered = minaug_bordered(ctx);          // option fold_bordered, read once per call
     // one evaluation of the fold residual (:16-38) at (x, pc): F, and sigma with the bordered vectors v, w of this point, which
     // the Newton step at the same point reuses (the reference solves them again in _get_bordered_terms, :71-99)
     auto point = [&](double* r, int* itl) -> int {
@@ -240,7 +335,8 @@ int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
         {
             JPair jp;
             BK_TRY(jp.make(prob, x, par, nparams));
-            BK_TRY(fold_terms(ctx, jp.J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it));
+            if (bordered) BK_TRY(fold_terms_bordered(ctx, jp.J, n, a, b, *lsopts, pl, zero, v, w, sigma, &cv, it));
+            else BK_TRY(fold_terms(ctx, jp.J, n, a, b, *bopts, *lsopts, pl, zero, v, w, sigma, &cv, it));
         }
         *itl = it[0] + it[1];
         if (!cv) ctx->diag.fold_unconverged += 1.0;
@@ -257,7 +353,10 @@ int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
         {
             JPair jp;
             BK_TRY(jp.make(prob, x, par, nparams));
-            BK_TRY(fold_linsolve(ctx, prob, jp.J, x, par, nparams, ipar, v, w, 1, rhsu, rhsp, *lsopts, pl, dXs, dsig, &cv, itl));
+            if (bordered)
+                BK_TRY(fold_linsolve_bordered(ctx, prob, jp.J, x, par, nparams, ipar, v, w, 1, rhsu, rhsp, *lsopts, pl, dXs, dsig, &cv, itl));
+            else
+                BK_TRY(fold_linsolve(ctx, prob, jp.J, x, par, nparams, ipar, v, w, 1, rhsu, rhsp, *lsopts, pl, dXs, dsig, &cv, itl));
         }
         if (!cv) ctx->diag.fold_unconverged += 1.0;
         BK_TRY(v_axpby(ctx, n, -1.0, dX, 1.0, x));

@@ -65,6 +65,18 @@ int minaug_update(bk_ctx* ctx, size_t n, const MinAugSolves& S, int nrhs, const 
     return 0;
 }
 
+// Context option fold_bordered (default 0 = the solves above): the formulation runs on bordered systems that stay regular where J is
+// singular, each ONE GMRES on [J a; b' c] left-preconditioned by diag(Pl, 1) (bordered.hip: bls_matrixfree_pl).
+bool minaug_bordered(bk_ctx* ctx) { return ctx->opt("fold_bordered", 0.0) != 0.0; }
+
+// [J a; b' c][u1; u2] = [rhst; rhsb] with an m-column border (fold: m = 1; the shape is what a Hopf system on (re, im) pairs with a
+// two-scalar border would hand over, m = 2 and c 2 x 2 row-major).  atil (optional): Pl^-1 a_j shared between solves.
+int minaug_bordered_solve(bk_ctx* ctx, bk_op* J, int m, const double* const* a, const double* const* b, const double* c,
+                          const double* rhst, const double* rhsb, const bk_gmres_opts& lo, bk_precond* pl, double* u1, double* u2,
+                          GmresResult* res, const double* const* atil = nullptr) {
+    return bls_matrixfree_pl(ctx, J, m, a, b, 1.0, c, rhst, rhsb, false, 0.0, lo, pl, u1, u2, res, atil);
+}
+
 // the right-hand sides and outputs of bk_fold_linsolve / bk_hopf_linsolve (`what`)
 int minaug_check_rhs(bk_ctx* ctx, const char* what, int nrhs, const double* const* rhsu, double* const* dX) {
     if (nrhs < 1 || nrhs > 2) return set_error(ctx, "%s: 1 or 2 right-hand sides (got %d)", what, nrhs);

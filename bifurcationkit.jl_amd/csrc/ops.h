@@ -301,6 +301,21 @@ int bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, do
                   double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_bordering_opts& bo,
                   const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2],
                   double* xnew = nullptr);
+// The operator of a left-preconditioned solve for operators built on top of it (solver.hip: ShiftPrecOp behind prec_op_create;
+// delete `op` after the solve).  The solve is about alpha0 I + alpha1 op: (0, 1) on the literal chain, the solve's
+// (t_alpha0, t_alpha1) in stencil-free mode (tmode), where op applies T.
+struct PrecOpView {
+    bk_op* op = nullptr;
+    bool tmode = false;
+    double alpha0 = 0.0, alpha1 = 1.0;
+};
+int prec_op_create(bk_ctx* ctx, bk_op* J, bk_precond* pl, double a0, double a1, int order, double* tmp, PrecOpView* out);
+// MatrixFreeBLS with the left preconditioner diag(Pl, 1) (bordered.hip): ONE GMRES on
+//     diag(Pl^-1, 1) [J + shift I, a; bscale b', c] [u1; u2] = [Pl^-1 rhst; rhsb],      m columns, c row-major m x m.
+// atil (optional): the m vectors Pl^-1 a_j when the caller has them already (solves that share a border column).
+int bls_matrixfree_pl(bk_ctx* ctx, bk_op* J, int m, const double* const* a, const double* const* b, double bscale, const double* c,
+                      const double* rhst, const double* rhsb, bool has_shift, double shift, const bk_gmres_opts& ls, bk_precond* pl,
+                      double* u1, double* u2, GmresResult* res, const double* const* atil = nullptr);
 // callback(state; fromNewton) of the Newton correctors (solver.hip, minaug.h): the cbMaxNorm veto, then the user's function;
 // 0 = stop
 int newton_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear, double p,

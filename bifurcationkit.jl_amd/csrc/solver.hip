@@ -2,6 +2,7 @@
 //   gmres_core / linsolve   GMRESKrylovKit + GMRESIterativeSolvers      src/LinearSolver.jl:149-291
 //   bk_bls_bordering        BorderingBLS (BEC + k refinements)           src/LinearBorderSolver.jl:88-166
 //   bk_bls_matrixfree       MatrixFreeBLS on BorderedArray(u, p)         src/LinearBorderSolver.jl:326-335,424-437
+//                           (with the left preconditioner diag(Pl, 1): bordered.hip, on prec_op_create below)
 //   bk_eig_shiftinvert      ShiftInvert + Krylov-Schur outer iteration   src/EigSolver.jl:246-266, examples/SH3d.jl:96-113
 //   bk_newton               _newton                                      src/Newton.jl:66-114
 //   bk_newton_palc          newton_palc                                  src/continuation/Palc.jl:187-305
@@ -982,6 +983,22 @@ struct ShiftPrecOp : bk_op {
 };
 
 }  // namespace
+
+// The operator of a left-preconditioned solve as an object of its own, for operators built on top of it (bordered.hip): the
+// ShiftPrecOp linsolve would set up for (J, pl, a0, a1) -- order 0: a0 + a1 Pl^-1 J, order 1: Pl^-1 (a0 + a1 J) -- in whichever mode
+// init_fold chooses.  tmp: n doubles owned by the caller.
+int prec_op_create(bk_ctx* ctx, bk_op* J, bk_precond* pl, double a0, double a1, int order, double* tmp, PrecOpView* out) {
+    ShiftPrecOp* W = new ShiftPrecOp;
+    W->ctx = ctx; W->n = J->n; W->ntail = 0;
+    W->J = J; W->P = pl; W->a0 = a0; W->a1 = a1; W->order = order; W->tmp = tmp;
+    const int e = W->init_fold();
+    if (e != 0) { delete W; return e; }
+    out->op = W;
+    out->tmode = W->tmode;
+    out->alpha0 = W->tmode ? W->t_alpha0 : 0.0;
+    out->alpha1 = W->tmode ? W->t_alpha1 : 1.0;
+    return 0;
+}
 
 // ================================================================== symmetric Krylov.jl solvers (KrylovLS :minres / :cg)
 // Paige-Saunders MINRES for the symmetric operator v -> a0 v + a1 J v with the SPD preconditioner M^-1 = Pl^-1

@@ -726,11 +726,22 @@ class BorderingBLS:
 @dataclass
 class MatrixFreeBLS:
     """src/LinearBorderSolver.jl:404-437 on BorderedArray(u, p): one GMRES on the (N+1) operator
-    MatrixFreeBLSmap (:326-335), device-resident with the scalar border on the host."""
+    MatrixFreeBLSmap (:326-335), device-resident with the scalar border on the host.
+
+    ``use_pl = True`` carries the solver's left preconditioner into the bordered system as diag(Pl, 1) (bk_bls_matrixfree_pl,
+    bk_bls_block_matrixfree_pl): the solve that stays regular where J is singular.  ``use_pl = False`` (default): the
+    unpreconditioned operator, as before."""
     solver: _GMRES = None
+    use_pl: bool = False
 
     def update_bls(self, ls):
-        return MatrixFreeBLS(ls)
+        return MatrixFreeBLS(ls, self.use_pl)
+
+    def _need_pl(self):
+        pl = self.solver._pl()
+        if pl is None:
+            raise TypeError("MatrixFreeBLS(use_pl=True) needs a solver with a left preconditioner Pl")
+        return pl
 
     def __call__(self, J, dR, dzu, dzp, R, n, xiu=1.0, xip=1.0, *, shift=None, dotp=None, dotscale=None):
         if not isinstance(self.solver, _GMRES) or not isinstance(R, HipVec):
@@ -741,6 +752,13 @@ class MatrixFreeBLS:
         dX = R.similar()
         dl, cv, it = C.c_double(), C.c_int(), C.c_int()
         lo = self.solver._opts()
+        if self.use_pl:
+            ctx.check(ctx.lib.bk_bls_matrixfree_pl(
+                ctx.h, J.h, _ptr(dR.t), _ptr(dzu.t), float(dzp), _ptr(R.t), float(n), float(xiu), float(xip),
+                0 if shift is None else 1, 0.0 if shift is None else float(shift),
+                1.0 if dotscale is None else float(dotscale), C.byref(lo), self._need_pl(), _ptr(dX.t), C.byref(dl), C.byref(cv),
+                C.byref(it)), "bk_bls_matrixfree_pl")
+            return dX, dl.value, bool(cv.value), it.value
         ctx.check(ctx.lib.bk_bls_matrixfree(
             ctx.h, J.h, _ptr(dR.t), _ptr(dzu.t), float(dzp), _ptr(R.t), float(n), float(xiu), float(xip),
             0 if shift is None else 1, 0.0 if shift is None else float(shift),
@@ -765,6 +783,12 @@ class MatrixFreeBLS:
         u2 = (C.c_double * m)()
         cv, it = C.c_int(), C.c_int()
         lo = self.solver._opts()
+        if self.use_pl:
+            ctx.check(ctx.lib.bk_bls_block_matrixfree_pl(ctx.h, J.h, m, ap, bp, cc, _ptr(rhst.t), rb, 0 if shift is None else 1,
+                                                         0.0 if shift is None else float(shift), float(dotscale), C.byref(lo),
+                                                         self._need_pl(), _ptr(u1.t), u2, C.byref(cv), C.byref(it)),
+                      "bk_bls_block_matrixfree_pl")
+            return u1, np.array(list(u2)), bool(cv.value), it.value
         ctx.check(ctx.lib.bk_bls_block_matrixfree(ctx.h, J.h, m, ap, bp, cc, _ptr(rhst.t), rb, 0 if shift is None else 1,
                                                   0.0 if shift is None else float(shift), float(dotscale), C.byref(lo),
                                                   _ptr(u1.t), u2, C.byref(cv), C.byref(it)), "bk_bls_block_matrixfree")

@@ -318,6 +318,28 @@ int bk_bls_block_matrixfree(bk_ctx* ctx, bk_op* J, int m, const double* const* a
                             double shift, double dotscale, const bk_gmres_opts* lsopts, double* u1,
                             double* u2, int* converged, int* itlinear);
 
+/* MatrixFreeBLS with the solver's LEFT preconditioner carried into the bordered system as diag(Pl, 1): the arguments of
+ * bk_bls_matrixfree / bk_bls_block_matrixfree plus pl (required).  ONE GMRES on
+ *     out.u = Pl^-1 ((J + shift I) x.u) + sum_j x.p[j] (Pl^-1 a_j) ,   out.p = c x.p + [xi_u dotscale <b_i, x.u>]_i
+ * (MatrixFreeBLSmap, src/LinearBorderSolver.jl:326-352, under the preconditioned map of src/LinearSolver.jl:270-278) with the
+ * right-hand side (Pl^-1 R, n): the top preconditioned, the tail untouched.  The unbordered part runs as the preconditioned
+ * operator of bk_gmres does (stencil-free where the plan allows it, option gmres_stencil_free); stopping rules and the explicit
+ * residual check are those of the GMRES flavor, on the BorderedArray norm of the PRECONDITIONED system.  MINRES / CG flavors, a
+ * right preconditioner and ranks > 1 are refused.  Regular where J itself is singular (folds, branch points).             */
+int bk_bls_matrixfree_pl(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp,
+                         const double* R, double n, double xiu, double xip, int has_shift,
+                         double shift, double dotscale, const bk_gmres_opts* lsopts, bk_precond* pl,
+                         double* dX, double* dl, int* converged, int* itlinear);
+int bk_bls_block_matrixfree_pl(bk_ctx* ctx, bk_op* J, int m, const double* const* a, const double* const* b,
+                               const double* c, const double* rhst, const double* rhsb, int has_shift,
+                               double shift, double dotscale, const bk_gmres_opts* lsopts, bk_precond* pl,
+                               double* u1, double* u2, int* converged, int* itlinear);
+/* The per-application pass of that operator, exposed for exact tests: y[i] += sum_j coef[j] atil[j][i] in place (every product
+ * and every sum rounded on its own, in j order) and dots[j] = <b[j], x> (deterministic two-stage sum, all-reduced), j < m <=
+ * BK_MAX_BORDER, in ONE pass over y, x, the m atil and the m b: (3 + 2 m) 8 n bytes.  y must not alias another operand.   */
+int bk_bordered_tail(bk_ctx* ctx, size_t n, int m, double* y, const double* x, const double* const* atil,
+                     const double* const* b, const double* coef, double* dots);
+
 /* ------------------------------------------------------------------ eigensolver ------------
  * (eig::ShiftInvert)(J, nev) -> (vals, vecs, converged, niter): src/EigSolver.jl:246-266 with a
  * Krylov-Schur (KrylovKit.eigsolve-style) outer iteration; the SH3dEig of examples/SH3d.jl:96-113.
@@ -530,6 +552,21 @@ int bk_newton_fold(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
                    const double* a, const double* b, const bk_newton_opts* nopts, const bk_bordering_opts* bopts,
                    const bk_gmres_opts* lsopts, bk_precond* pl, double* v, double* w, double* sigma,
                    bk_newton_result* res);
+/* The border row of the full fold Jacobian as a vector (MinAugFold.jl:136-145, the branch without `usehessian`):
+ * sigx[i] = -w[i] h(u[i]) v[i] with h the pointwise Hessian factor of bk_d2f, so that <sigx, X> = -<w, d2F(u)[v, X]> for every
+ * X; one streaming pass, sigx must not alias u, v or w.  sigma_p (may be NULL) = -<w, dJ/dp v> for params[ipar] as
+ * bk_fold_contract returns it.
+ * Context option "fold_bordered" (default 0, read once per call by bk_fold_terms, bk_fold_linsolve and bk_newton_fold; no option
+ * struct changes).  At 1 the formulation runs on the system that is REGULAR at the fold instead of on J \ a, J \ F, J \ dpF
+ * ("Careful, this method makes the linear system singular", :149):
+ *   bk_fold_terms     (v, sigma) from ONE solve [J a; b' 0][v; sigma] = [0; 1] with bk_bls_matrixfree_pl (w: the adjoint system
+ *                     the same way, or w = v for a == b); bopts is not read; itlinear[0] / [1] = the two GMRES counts;
+ *   bk_fold_linsolve  [J dpF; sigx' sigma_p][dX_k; dsigma_k] = [rhsu_k; rhsp_k], one such solve per right-hand side, all
+ *                     sharing Pl^-1 dpF;
+ *   bk_newton_fold    runs on both; "fold_unconverged_solves" counts as before.
+ * pl must be given (the bordered operator is preconditioned by diag(Pl, 1)).                                               */
+int bk_fold_border(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, const double* v,
+                   const double* w, double* sigx, double* sigma_p);
 
 /* ------------------------------------------------------------------ Hopf points (codim 2) ---------------
  * The minimally augmented Hopf formulation of src/codim2/MinAugHopf.jl, matrix-free: unknowns (x, p = params[ipar], omega),
