@@ -166,6 +166,9 @@ SIGNATURES = {
     "bk_gmres_cshift": (I, [VP, VP, VP, VP, VP, VP, D, D, D, C.POINTER(GmresOpts), VP, c_int_p, c_int_p, c_double_p]),
     "bk_bls_bordering_cshift": (I, [VP, VP, VP, VP, VP, VP, D, D, VP, VP, D, D, D, D, D, D, D, C.POINTER(GmresOpts),
                                     VP, VP, VP, c_double_p, c_int_p, c_int_p]),
+    "bk_bls_matrixfree_pl_cshift": (I, [VP, VP, VP, VP, VP, VP, D, D, VP, VP, D, D, D, D, D, D, D, C.POINTER(GmresOpts),
+                                        VP, VP, VP, c_double_p, c_int_p, c_int_p]),
+    "bk_cbordered_tail": (I, [VP, SZ, VP, VP, VP, VP, VP, VP, VP, VP, c_double_p, c_double_p]),
     "bk_eig_shiftinvert": (I, [VP, VP, I, C.POINTER(EigOpts), C.POINTER(GmresOpts), VP, c_double_p, c_double_p,
                                VP, VP, SZ, c_int_p, c_int_p, c_int_p]),
     "bk_eig_set_start_vector": (I, [VP, VP]),

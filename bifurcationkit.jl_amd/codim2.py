@@ -129,6 +129,7 @@ class _fold_bordered:
     """Context option fold_bordered set to 1 around a native call and put back afterwards (the library reads it once per call).
     With ``on`` false nothing is touched.  An option cannot be unset: on a context that never had it, it is left at 0, which the
     library reads as the default path (tests/test_gpu_fold_bordered.py: unset and 0 give the same bits)."""
+    option = "fold_bordered"
 
     def __init__(self, ctx, on: bool):
         self.ctx, self.on = ctx, bool(on)
@@ -137,16 +138,32 @@ class _fold_bordered:
     def __enter__(self):
         if self.on:
             try:
-                self.prev = self.ctx.get_option("fold_bordered")
+                self.prev = self.ctx.get_option(self.option)
             except L.BkHipError:
                 self.prev = 0.0
-            self.ctx.set_option("fold_bordered", 1.0)
+            self.ctx.set_option(self.option, 1.0)
         return self
 
     def __exit__(self, *exc):
         if self.on:
-            self.ctx.set_option("fold_bordered", self.prev)
+            self.ctx.set_option(self.option, self.prev)
         return False
+
+
+class _hopf_bordered(_fold_bordered):
+    """The same for the context option hopf_bordered (tests/test_gpu_hopf_bordered.py: unset and 0 give the same bits)."""
+    option = "hopf_bordered"
+
+
+def _hopf_bordered_path(bls) -> bool:
+    """True when ``bls`` selects the Hopf bordered vectors (and the H21 solve of the Bautin normal form) on the system that is
+    regular at the Hopf point (context option hopf_bordered): MatrixFreeBLS(ls, use_pl=True), each bordered vector ONE GMRES on
+    [J - i omega, a; b^H, 0] left-preconditioned by diag(Pl, 1).  None or a BorderingBLS: block elimination, two shifted solves."""
+    if isinstance(bls, MatrixFreeBLS):
+        if not bls.use_pl:
+            raise TypeError("the Hopf formulation takes BorderingBLS or MatrixFreeBLS(ls, use_pl=True)")
+        return True
+    return False
 
 
 def fold_border(prob, x: HipVec, pars, ipar: int, v: HipVec, w: HipVec):
@@ -678,17 +695,19 @@ def hopf_contract(prob, x: HipVec, pars, ipar: int, v, w, X=()):
     return z[:m], z[m], z[m + 1]
 
 
-def hopf_terms(prob, x: HipVec, pars, ipar: int, omega: float, a, b, ls: _GMRES):
-    """bk_hopf_terms: (v, w, sigma, sigma_p, sigma_omega, converged, (itv, itw)); v, w as (re, im) pairs."""
+def hopf_terms(prob, x: HipVec, pars, ipar: int, omega: float, a, b, ls: _GMRES, bls: BorderingBLS | MatrixFreeBLS | None = None):
+    """bk_hopf_terms: (v, w, sigma, sigma_p, sigma_omega, converged, (itv, itw)); v, w as (re, im) pairs.  With
+    ``bls = MatrixFreeBLS(ls, use_pl=True)`` each of (v, sigma) and w is ONE preconditioned bordered solve (option hopf_bordered)."""
     ctx = prob.ctx
     vr, vi, wr, wi = x.similar(), x.similar(), x.similar(), x.similar()
     sg, spp, sw = (C.c_double * 2)(), (C.c_double * 2)(), (C.c_double * 2)()
     cv = C.c_int()
     it = (C.c_int * 2)()
     lo = ls._opts()
-    ctx.check(ctx.lib.bk_hopf_terms(ctx.h, prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), float(omega), _cptr(a[0]),
-                                    _cptr(a[1]), _cptr(b[0]), _cptr(b[1]), C.byref(lo), ls._pl(), _ptr(vr.t), _ptr(vi.t),
-                                    _ptr(wr.t), _ptr(wi.t), sg, spp, sw, C.byref(cv), it), "bk_hopf_terms")
+    with _hopf_bordered(ctx, _hopf_bordered_path(bls)):
+        ctx.check(ctx.lib.bk_hopf_terms(ctx.h, prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar), float(omega), _cptr(a[0]),
+                                        _cptr(a[1]), _cptr(b[0]), _cptr(b[1]), C.byref(lo), ls._pl(), _ptr(vr.t), _ptr(vi.t),
+                                        _ptr(wr.t), _ptr(wi.t), sg, spp, sw, C.byref(cv), it), "bk_hopf_terms")
     return ((vr, vi), (wr, wi), complex(sg[0], sg[1]), complex(spp[0], spp[1]), complex(sw[0], sw[1]), bool(cv.value),
             (it[0], it[1]))
 
@@ -728,13 +747,13 @@ def hopf_point(br, ind: int) -> HopfVec:
     return HopfVec(x.copy(), [float(sp["param"]), abs(float(lam.imag))])
 
 
-def hopf_start_vectors(prob, X: HopfVec, ls: _GMRES, eig=None, nev=4, seed=0):
+def hopf_start_vectors(prob, X: HopfVec, ls: _GMRES, eig=None, nev=4, seed=0, bls=None):
     """(a, b) for newton_hopf / continuation_hopf at the guess X.  Default (continuation_hopf, :566-585): random complex a, b, then
     the bordered vectors of the guess, a = w/|w|, b = v/|v|.  With an eigensolver (start_with_eigen): b = zeta, the eigenvector
     of J(x, p) whose eigenvalue lambda is nearest i omega (``save_vectors``), a = zeta* from the adjoint bordered solve, scaled so
     that a^H b = 1.  The eigensolver keeps one (re, im) pair per conjugate pair; which member it describes is checked on J itself:
     J zr = Re(lambda) zr - Im(lambda) zi holds for the eigenvector of lambda, J zr = Re(lambda) zr + Im(lambda) zi for its
-    conjugate, whose imaginary part is then negated."""
+    conjugate, whose imaginary part is then negated.  ``bls``: as in hopf_terms."""
     x, (p, omega) = X.u, X.p
     pv = prob._pvec(p)
     if eig is None:
@@ -742,7 +761,7 @@ def hopf_start_vectors(prob, X: HopfVec, ls: _GMRES, eig=None, nev=4, seed=0):
         n = x.n
         a = tuple(HipVec.from_numpy(prob.ctx, rng.random(n), x.nglobal) for _ in range(2))
         b = tuple(HipVec.from_numpy(prob.ctx, rng.random(n), x.nglobal) for _ in range(2))
-        v, w, *_ = hopf_terms(prob, x, pv, prob.ipar, omega, a, b, ls)
+        v, w, *_ = hopf_terms(prob, x, pv, prob.ipar, omega, a, b, ls, bls)
         return _cscale(w, 1.0 / cnorm(w)), _cscale(v, 1.0 / cnorm(v))
     J = prob.jacobian(x, p)
     vals, vecs, _, _ = eig(J, nev)
@@ -758,18 +777,24 @@ def hopf_start_vectors(prob, X: HopfVec, ls: _GMRES, eig=None, nev=4, seed=0):
     if conj < own:
         zeta[1].scale_(-1.0)
     zeta = _cscale(zeta, 1.0 / cnorm(zeta))
-    _, w, *_ = hopf_terms(prob, x, pv, prob.ipar, omega, zeta, zeta, ls)
+    _, w, *_ = hopf_terms(prob, x, pv, prob.ipar, omega, zeta, zeta, ls, bls)
     c = cinner(w, zeta)
     return _cscale(w, 1.0 / c.conjugate()), zeta
 
 
 # ------------------------------------------------------------------------------------------ newton_hopf
-def newton_hopf(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=25, norm_inf=False):
+def newton_hopf(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=25, norm_inf=False,
+                bls: BorderingBLS | MatrixFreeBLS | None = None):
     """newton_hopf with HopfLinearSolverMinAug under _newton (src/Newton.jl:66-114), call by call on the plugin surface: the
     residual solves bls(J, a, b, 0, 0, 1; shift = -i omega) for (v, sigma) and bls(J', b, a, 0, 0, 1; shift = +i omega) for w
     (BorderingBLS.solve_complex); each Newton step is _hopf_MA_linear_solver's usehessian branch with ls(J, F, dpF) (bk_gmres2)
-    and one hopf_contract pass for S(x1), S(x2), w^H dJ/dp v and w^H v.  v, w of a point serve its residual and its step."""
-    bls = BorderingBLS(ls, check_precision=False)
+    and one hopf_contract pass for S(x1), S(x2), w^H dJ/dp v and w^H v.  v, w of a point serve its residual and its step.
+
+    ``bls = MatrixFreeBLS(ls, use_pl=True)``: the same two calls of the residual go to the preconditioned bordered solver
+    (MatrixFreeBLS.solve_complex), regular at the Hopf point, where J - i omega is not.  The Newton step is unchanged: J itself is
+    regular there."""
+    if not _hopf_bordered_path(bls):
+        bls = BorderingBLS(ls, check_precision=False)
     ipar = prob.ipar
     x, p, om = X0.u.copy(), float(X0.p[0]), float(X0.p[1])
     itlin, bad = 0, 0
@@ -804,8 +829,10 @@ def newton_hopf(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=2
                 sigma=sigma, unconverged_solves=bad)
 
 
-def newton_hopf_native(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=25, norm_inf=False, callback=None):
-    """The same as one library call (bk_newton_hopf)."""
+def newton_hopf_native(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_iterations=25, norm_inf=False, callback=None,
+                       bls: BorderingBLS | MatrixFreeBLS | None = None):
+    """The same as one library call (bk_newton_hopf); with ``bls = MatrixFreeBLS(ls, use_pl=True)`` under the context option
+    hopf_bordered = 1, set and put back around the call."""
     ctx = prob.ctx
     x = X0.u.copy()
     p, om = C.c_double(float(X0.p[0])), C.c_double(float(X0.p[1]))
@@ -816,9 +843,10 @@ def newton_hopf_native(prob, X0: HopfVec, a, b, ls: _GMRES, tol=1e-12, max_itera
     lo = ls._opts()
     res = L.NewtonResult()
     bad0 = ctx.get_option("hopf_unconverged_solves")
-    ctx.check(ctx.lib.bk_newton_hopf(ctx.h, prob.h, _ptr(x.t), C.byref(p), C.byref(om), _carr(pv), len(pv), prob.ipar,
-                                     _cptr(a[0]), _cptr(a[1]), _cptr(b[0]), _cptr(b[1]), C.byref(no), C.byref(lo), ls._pl(),
-                                     _ptr(vr.t), _ptr(vi.t), _ptr(wr.t), _ptr(wi.t), sigma, C.byref(res)), "bk_newton_hopf")
+    with _hopf_bordered(ctx, _hopf_bordered_path(bls)):
+        ctx.check(ctx.lib.bk_newton_hopf(ctx.h, prob.h, _ptr(x.t), C.byref(p), C.byref(om), _carr(pv), len(pv), prob.ipar,
+                                         _cptr(a[0]), _cptr(a[1]), _cptr(b[0]), _cptr(b[1]), C.byref(no), C.byref(lo), ls._pl(),
+                                         _ptr(vr.t), _ptr(vi.t), _ptr(wr.t), _ptr(wi.t), sigma, C.byref(res)), "bk_newton_hopf")
     return dict(u=HopfVec(x, [p.value, om.value]), converged=bool(res.converged), itnewton=res.itnewton,
                 itlineartot=res.itlinear, residuals=[res.residuals[i] for i in range(res.itnewton + 1)], v=(vr, vi), w=(wr, wi),
                 sigma=complex(sigma[0], sigma[1]),
@@ -835,8 +863,13 @@ class HopfProblem(_MinAugProblem):
     keep_vw = False                                 # detection on: update keeps the bordered vectors of the point in last_vw
     last_vw = None
 
+    def __init__(self, prob, lens2: str, a, b, ls: _GMRES, bls: BorderingBLS | MatrixFreeBLS | None = None):
+        super().__init__(prob, lens2, a, b, ls)
+        _hopf_bordered_path(bls)                    # refuses an unpreconditioned MatrixFreeBLS up front
+        self.bls = bls                              # MatrixFreeBLS(ls, use_pl=True): the bordered vectors on that path
+
     def _solve_terms(self, X: HopfVec, p2: float):
-        return hopf_terms(self.prob, X.u, self.pvec(X.p[0], p2), self.ipar1, X.p[1], self.a, self.b, self.ls)
+        return hopf_terms(self.prob, X.u, self.pvec(X.p[0], p2), self.ipar1, X.p[1], self.a, self.b, self.ls, self.bls)
 
     def _sigma_p(self, x, pv, ipar, v, w):
         """-w^H dJ/dp v"""
@@ -889,7 +922,7 @@ class HopfBranch(_MinAugBranch):
 
 def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls: _GMRES, cp: Cn.ContinuationPar, theta=0.5,
                       norm_inf=True, update_minaug_every_step=1, save_sol=False, ds_sequence=None, verbosity=0,
-                      detect_codim2=0) -> HopfBranch:
+                      detect_codim2=0, bls: BorderingBLS | MatrixFreeBLS | None = None) -> HopfBranch:
     """continuation_hopf(prob, alg = PALC(tangent = Secant()), hopfpointguess, par, lens1, lens2, a, b, options_cont) with
     jacobian_ma = MinAug(): PALC on G(X, p2) through continuation.newton_palc with BorderingBLS(solver = HopfLinearSolverMinAug(),
     check_precision = false), Secant tangent, the two starting points of continuation by newton on G, step-size control of
@@ -903,9 +936,12 @@ def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls
     br.l1 (b) and br.GH (Re b; the previous value when |Re b| >= 1e5, :632), and every sign change of GH between consecutive
     points goes to br.specialpoint as type "gh" with the bracketing p2 interval.  2: each sign change is bisected along the curve
     (_locate_gh) and the special point keeps the located state; the curve continues from the state it had before the bisection,
-    so the recorded points are those of detect_codim2 = 1.  Bogdanov-Takens, zero-Hopf and Hopf-Hopf points are not located."""
+    so the recorded points are those of detect_codim2 = 1.  Bogdanov-Takens, zero-Hopf and Hopf-Hopf points are not located.
+
+    ``bls`` (optional): the bordered solver of the formulation's bordered vectors -- MatrixFreeBLS(ls, use_pl=True) takes each from
+    ONE preconditioned bordered solve (option hopf_bordered).  The PALC border and the Newton step of G stay as they are."""
     br = HopfBranch(lens2=lens2)
-    P = HopfProblem(prob, lens2, a, b, ls)
+    P = HopfProblem(prob, lens2, a, b, ls, bls)
     P.keep_vw = bool(detect_codim2)
     if detect_codim2 and update_minaug_every_step != 1:
         raise ValueError("detect_codim2 needs the bordered vectors of every point (update_minaug_every_step = 1)")
@@ -1262,12 +1298,13 @@ def _bautin_record(hopf: Hopf, lens2, G21, G32, H20, H30, H21, H31, H22, cv, it,
                   type=bautin_type(l2), converged=bool(cv), itlinear=tuple(int(i) for i in it), unconverged_solves=bad)
 
 
-def bautin_normal_form(prob, hopf: Hopf, ls: _GMRES, lens2=None) -> Bautin:
+def bautin_normal_form(prob, hopf: Hopf, ls: _GMRES, lens2=None, bls: BorderingBLS | MatrixFreeBLS | None = None) -> Bautin:
     """bautin_normal_form (:642-829, detailed = false) call by call on the plugin surface at the Hopf point of the record ``hopf``
     (hopf_normal_form / hopf_normal_form_native: x0, params, omega, zeta, zeta*, Psi110, Psi200, b): H30 =
     ls.solve_complex(J, h30, a0 = 3 i omega, a1 = -1), H21 = BorderingBLS(ls, check_precision = false).solve_complex(J, q, p0, 0,
     h21, 0; shift = -i omega), H31 = ls.solve_complex(J, h31, a0 = 2 i omega, a1 = -1), H22 = -ls(J, h22); the right-hand sides
-    from bautin_rhs3 / bautin_rhs4 and G32 from bautin_contract."""
+    from bautin_rhs3 / bautin_rhs4 and G32 from bautin_contract.  ``bls = MatrixFreeBLS(ls, use_pl=True)`` takes H21, whose
+    J - i omega is singular, from ONE preconditioned bordered solve (MatrixFreeBLS.solve_complex)."""
     from .hip import HipJacobian
     x, om, pv = hopf.x0, float(hopf.omega), list(hopf.params)
     q, p0 = hopf.zeta, hopf.zeta_star
@@ -1280,7 +1317,8 @@ def bautin_normal_form(prob, hopf: Hopf, ls: _GMRES, lens2=None) -> Bautin:
     J = HipJacobian(prob, x, pv)
     h30, h21 = bautin_rhs3(prob, x, pv, q, H20, H11, G21)
     H30, cv30, it30 = ls.solve_complex(J, h30, a0=complex(0.0, 3.0 * om), a1=-1.0)
-    H21, _, cv21, it21 = BorderingBLS(ls, check_precision=False).solve_complex(J, q, p0, 0.0, h21, 0.0, shift=complex(0.0, -om))
+    bls21 = bls if _hopf_bordered_path(bls) else BorderingBLS(ls, check_precision=False)
+    H21, _, cv21, it21 = bls21.solve_complex(J, q, p0, 0.0, h21, 0.0, shift=complex(0.0, -om))
     h31, h22 = bautin_rhs4(prob, x, pv, q, H20, H11, H30, H21, G21)
     H31, cv31, it31 = ls.solve_complex(J, h31, a0=complex(0.0, 2.0 * om), a1=-1.0)
     H22, cv22, it22 = ls(J, h22)
@@ -1290,8 +1328,9 @@ def bautin_normal_form(prob, hopf: Hopf, ls: _GMRES, lens2=None) -> Bautin:
                           (it30, int(np.sum(it21)), it31, it22))
 
 
-def bautin_normal_form_native(prob, hopf: Hopf, ls: _GMRES, lens2=None) -> Bautin:
-    """The same as one library call (bk_bautin_normal_form)."""
+def bautin_normal_form_native(prob, hopf: Hopf, ls: _GMRES, lens2=None, bls: BorderingBLS | MatrixFreeBLS | None = None) -> Bautin:
+    """The same as one library call (bk_bautin_normal_form); with ``bls = MatrixFreeBLS(ls, use_pl=True)`` under the context option
+    hopf_bordered = 1, set and put back around the call."""
     ctx = prob.ctx
     x, om, pv = hopf.x0, float(hopf.omega), list(hopf.params)
     H30, H21, H31, H22 = (x.similar(), x.similar()), (x.similar(), x.similar()), (x.similar(), x.similar()), x.similar()
@@ -1303,25 +1342,28 @@ def bautin_normal_form_native(prob, hopf: Hopf, ls: _GMRES, lens2=None) -> Bauti
     it = (C.c_int * 4)()
     lo = ls._opts()
     bad0 = ctx.get_option("bautin_unconverged_solves")
-    ctx.check(ctx.lib.bk_bautin_normal_form(ctx.h, prob.h, _ptr(x.t), _carr(pv), len(pv), om, *_c2(hopf.zeta), *_c2(hopf.zeta_star),
-                                            _ptr(hopf.nf.Psi110.t), *_c2(hopf.nf.Psi200), ab, C.byref(lo), ls._pl(), *_c2(H30),
-                                            *_c2(H21), *_c2(H31), _ptr(H22.t), g, C.byref(cv), it), "bk_bautin_normal_form")
+    with _hopf_bordered(ctx, _hopf_bordered_path(bls)):
+        ctx.check(ctx.lib.bk_bautin_normal_form(ctx.h, prob.h, _ptr(x.t), _carr(pv), len(pv), om, *_c2(hopf.zeta),
+                                                *_c2(hopf.zeta_star), _ptr(hopf.nf.Psi110.t), *_c2(hopf.nf.Psi200), ab, C.byref(lo),
+                                                ls._pl(), *_c2(H30), *_c2(H21), *_c2(H31), _ptr(H22.t), g, C.byref(cv), it),
+                  "bk_bautin_normal_form")
     H20 = tuple(v.copy().scale_(2.0) for v in hopf.nf.Psi200)
     return _bautin_record(hopf, lens2, complex(g[0], g[1]), complex(g[2], g[3]), H20, H30, H21, H31, H22, cv.value,
                           (it[0], it[1], it[2], it[3]), int(ctx.get_option("bautin_unconverged_solves") - bad0))
 
 
-def _bautin_from_branch(br, ind: int, prob, ls: _GMRES, tol, max_iterations, norm_inf) -> Bautin:
+def _bautin_from_branch(br, ind: int, prob, ls: _GMRES, tol, max_iterations, norm_inf, bls=None) -> Bautin:
     """A "gh" point of a HopfBranch: newton_hopf_native at the located p2 from the located state -> hopf_eigenpair ->
     hopf_normal_form_native -> bautin_normal_form_native (the normal form at the REFINED Hopf point of the located p2)."""
     sp = br.specialpoint[ind]
     with _lens2_at(prob, br.lens2, sp["p2"]):
-        s = newton_hopf_native(prob, sp["x"], sp["a"], sp["b"], ls, tol=tol, max_iterations=max_iterations, norm_inf=norm_inf)
+        s = newton_hopf_native(prob, sp["x"], sp["a"], sp["b"], ls, tol=tol, max_iterations=max_iterations, norm_inf=norm_inf,
+                               bls=bls)
         if not s["converged"]:
             raise RuntimeError(f"get_normal_form: newton_hopf did not converge from the located point (residuals {s['residuals']})")
         zeta, zeta_star = hopf_eigenpair(prob, s)
         hp = hopf_normal_form_native(prob, s["u"], zeta, zeta_star, ls)
-        return bautin_normal_form_native(prob, hp, ls, lens2=br.lens2)
+        return bautin_normal_form_native(prob, hp, ls, lens2=br.lens2, bls=bls)
 
 
 def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, max_iterations=15, norm_inf=False, seed=0,
@@ -1333,12 +1375,13 @@ def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, 
     type "bp" or "fold" goes to normal_form1d.get_normal_form1d (``bls``, ``refine`` as there) and returns its SimpleBranchPoint;
     "nd" points, and "bp" / "fold" points of any other problem, have no normal form here.  A point of type "gh" of a HopfBranch
     (continuation_hopf(..., detect_codim2 > 0)) returns its Bautin record: newton_hopf_native at the located p2 ->
-    hopf_eigenpair -> hopf_normal_form_native -> bautin_normal_form_native."""
+    hopf_eigenpair -> hopf_normal_form_native -> bautin_normal_form_native.  For "hopf" and "gh" points ``bls`` is the bordered
+    solver of newton_hopf_native and bautin_normal_form_native (MatrixFreeBLS(ls, use_pl=True): option hopf_bordered)."""
     from . import normal_form1d as N1
     sh = N1.is_sh_problem(prob)                     # decided before the branch is looked at
     kind = br.specialpoint[ind].get("type")
     if kind == "gh" and isinstance(br, HopfBranch):
-        return _bautin_from_branch(br, ind, prob, ls, tol, max_iterations, norm_inf)
+        return _bautin_from_branch(br, ind, prob, ls, tol, max_iterations, norm_inf, bls)
     if sh and kind in ("bp", "fold"):
         return N1.get_normal_form1d(br, ind, prob, ls, bls=bls, eig=eig, nev=nev, refine=refine, tol=tol,
                                     max_iterations=max_iterations, norm_inf=norm_inf)
@@ -1347,8 +1390,8 @@ def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, 
                                   "available -- fold and branch points have refinement (newton_fold) and fold-curve continuation "
                                   "(continuation_fold), no normal form")
     X = hopf_point(br, ind)
-    a, b = hopf_start_vectors(prob, X, ls, eig=eig, nev=nev, seed=seed)
-    s = newton_hopf_native(prob, X, a, b, ls, tol=tol, max_iterations=max_iterations, norm_inf=norm_inf)
+    a, b = hopf_start_vectors(prob, X, ls, eig=eig, nev=nev, seed=seed, bls=bls)
+    s = newton_hopf_native(prob, X, a, b, ls, tol=tol, max_iterations=max_iterations, norm_inf=norm_inf, bls=bls)
     if not s["converged"]:
         raise RuntimeError(f"get_normal_form: newton_hopf did not converge from the bisected point (residuals {s['residuals']})")
     zeta, zeta_star = hopf_eigenpair(prob, s)

@@ -325,8 +325,16 @@ int bk_bautin_normal_form(bk_ctx* ctx, bk_problem* prob, const double* x, const 
     int cv30 = 0, it30 = 0, cv21 = 0, it21[2] = {0, 0}, cv31 = 0, it31 = 0;
     double dl[2];
     BK_TRY(bk_gmres_cshift(ctx, jp.J, w[2], w[3], h30_re, h30_im, 0.0, 3.0 * omega, -1.0, lsopts, pl, &cv30, &it30, nullptr));
-    BK_TRY(bk_bls_bordering_cshift(ctx, jp.J, z_re, z_im, zs_re, zs_im, 0.0, 0.0, w[4], w[5], 0.0, 0.0, 1.0, 1.0, 0.0, -omega, 1.0,
-                                   lsopts, pl, h21_re, h21_im, dl, &cv21, it21));
+    if (minaug_hopf_bordered(ctx)) {                // J - i omega is singular here: the bordered system in ONE preconditioned solve
+        GmresResult r21;
+        BK_TRY(minaug_hopf_bordered_solve(ctx, jp.J, z_re, z_im, zs_re, zs_im, w[4], w[5], 0.0, -omega, *lsopts, pl, h21_re, h21_im,
+                                          dl, &r21));
+        cv21 = r21.converged;
+        it21[0] = r21.niter;
+    } else {
+        BK_TRY(bk_bls_bordering_cshift(ctx, jp.J, z_re, z_im, zs_re, zs_im, 0.0, 0.0, w[4], w[5], 0.0, 0.0, 1.0, 1.0, 0.0, -omega, 1.0,
+                                       lsopts, pl, h21_re, h21_im, dl, &cv21, it21));
+    }
     // H31, H22
     BK_TRY(v_bautin_rhs4(ctx, n, c, {x, z_re, z_im, h20r, h20i, psi110, h30_re, h30_im, h21_re, h21_im}, g21, {w[2], w[3], w[4]}));
     BK_TRY(bk_gmres_cshift(ctx, jp.J, w[2], w[3], h31_re, h31_im, 0.0, 2.0 * omega, -1.0, lsopts, pl, &cv31, &it31, nullptr));

@@ -89,6 +89,15 @@ int stack(bk_ctx* ctx, size_t N, const double* re, const double* im, double* out
 
 }  // namespace
 
+// ComplexShiftOp as an object of its own, for operators built on top of it (bordered.hip: PlCBorderedOp)
+int bk::cshift_op_create(bk_ctx* ctx, bk_op* J, bk_precond* pl, double a0r, double a0i, double a1, int order, double* tmp, bk_op** out) {
+    ComplexShiftOp* W = new ComplexShiftOp;
+    W->ctx = ctx; W->n = 2 * J->n; W->ntail = 0; W->N = J->n;
+    W->J = J; W->P = pl; W->a0r = a0r; W->a0i = a0i; W->a1 = a1; W->order = order; W->tmp = tmp;
+    *out = W;
+    return 0;
+}
+
 extern "C" {
 
 int bk_gmres_cshift(bk_ctx* ctx, bk_op* J, const double* rhs_re, const double* rhs_im, double* x_re, double* x_im,

@@ -134,11 +134,22 @@ int norm_hopf(bk_ctx* ctx, size_t n, const double* f, const double sigma[2], boo
 }
 
 // _compute_bordered_vectors (:49-64): v, sigma from bls(J, a, b, 0, 0, 1; shift = -i omega), w from the adjoint handle,
-// bls(J', b, a, 0, 0, 1; shift = +i omega).  One BorderingBLS BEC pass each (bk_bls_bordering_cshift).
+// bls(J', b, a, 0, 0, 1; shift = +i omega).  One BorderingBLS BEC pass each (bk_bls_bordering_cshift); with `bordered` (context
+// option hopf_bordered) ONE preconditioned solve of each bordered system, which stays regular at the Hopf point (minaug.h).
 int hopf_terms(bk_ctx* ctx, bk_op* J, bk_op* Jt, size_t n, double omega, const double* ar, const double* ai, const double* br,
                const double* bi, const bk_gmres_opts& lo, bk_precond* pl, double* zero, double* vr, double* vi, double* wr,
-               double* wi, double sigma[2], int* cv, int it[2]) {
+               double* wi, double sigma[2], int* cv, int it[2], bool bordered) {
     BK_TRY(v_zero(ctx, n, zero));
+    if (bordered) {
+        GmresResult r1, r2;
+        double s2[2];
+        BK_TRY(minaug_hopf_bordered_solve(ctx, J, ar, ai, br, bi, zero, nullptr, 1.0, -omega, lo, pl, vr, vi, sigma, &r1));
+        BK_TRY(minaug_hopf_bordered_solve(ctx, Jt, br, bi, ar, ai, zero, nullptr, 1.0, omega, lo, pl, wr, wi, s2, &r2));
+        *cv = r1.converged & r2.converged;
+        it[0] = r1.niter;
+        it[1] = r2.niter;
+        return 0;
+    }
     int c1 = 0, c2 = 0, i1[2] = {0, 0}, i2[2] = {0, 0};
     double s2[2];
     BK_TRY(bk_bls_bordering_cshift(ctx, J, ar, ai, br, bi, 0.0, 0.0, zero, nullptr, 1.0, 0.0, 1.0, 1.0, 0.0, -omega, 1.0, &lo, pl,
@@ -245,7 +256,7 @@ int bk_hopf_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* 
         JPair jp;
         BK_TRY(jp.make(prob, x, params, nparams, true));
         BK_TRY(hopf_terms(ctx, jp.J, jp.Jt, n, omega, a_re, a_im, b_re, b_im, *lsopts, pl, zero, v_re, v_im, w_re, w_im, sigma,
-                          &cv, it));
+                          &cv, it, minaug_hopf_bordered(ctx)));
     }
     if (sigma_p || sigma_omega) {
         double s[4];
@@ -306,6 +317,7 @@ int bk_newton_hopf(bk_ctx* ctx, bk_problem* prob, double* x, double* p, double* 
     double par[BK_MAX_PARAMS];
     for (int i = 0; i < nparams; ++i) par[i] = params[i];
     double pc = *p, wc = *omega;
+    const bool bordered = minaug_hopf_bordered(ctx);         // option hopf_bordered, read once per call
     // one evaluation of the Hopf residual (:22-45) at (x, pc, wc), with the bordered vectors v, w of this point, which the
     // Newton step at the same point reuses (the reference solves them again in _get_bordered_terms)
     auto point = [&](double* r, int* itl) -> int {
@@ -315,7 +327,7 @@ int bk_newton_hopf(bk_ctx* ctx, bk_problem* prob, double* x, double* p, double* 
             JPair jp;
             BK_TRY(jp.make(prob, x, par, nparams, true));
             BK_TRY(hopf_terms(ctx, jp.J, jp.Jt, n, wc, a_re, a_im, b_re, b_im, *lsopts, pl, zero, v_re, v_im, w_re, w_im, sigma,
-                              &cv, it));
+                              &cv, it, bordered));
         }
         *itl = it[0] + it[1];
         if (!cv) ctx->diag.hopf_unconverged += 1.0;

@@ -77,6 +77,21 @@ int minaug_bordered_solve(bk_ctx* ctx, bk_op* J, int m, const double* const* a, 
     return bls_matrixfree_pl(ctx, J, m, a, b, 1.0, c, rhst, rhsb, false, 0.0, lo, pl, u1, u2, res, atil);
 }
 
+// Context option hopf_bordered (default 0 = BorderingBLS, two shifted solves per bordered vector): a bordered system
+// [shift + J, a; b^H, 0][X; l] = [R; n] on (re, im) pairs as ONE GMRES left-preconditioned by diag(Pl, 1) (bordered.hip:
+// bls_matrixfree_pl_cshift), regular where shift + J is singular -- the bordered vectors of hopf.hip and the H21 solve of bautin.hip.
+bool minaug_hopf_bordered(bk_ctx* ctx) { return ctx->opt("hopf_bordered", 0.0) != 0.0; }
+int minaug_hopf_bordered_solve(bk_ctx* ctx, bk_op* J, const double* ar, const double* ai, const double* br, const double* bi,
+                               const double* Rr, const double* Ri, double nr, double shift_im, const bk_gmres_opts& lo,
+                               bk_precond* pl, double* Xr, double* Xi, double l[2], GmresResult* res) {
+    if (!pl) return set_error(ctx, "hopf: hopf_bordered = 1 needs the left preconditioner");
+    const double* const a[2] = {ar, ai};
+    const double* const b[2] = {br, bi};
+    const double* const R[2] = {Rr, Ri};
+    const double c[2] = {0.0, 0.0}, nn[2] = {nr, 0.0}, shift[2] = {0.0, shift_im};
+    return bls_matrixfree_pl_cshift(ctx, J, a, b, 1.0, c, R, nn, shift, lo, pl, Xr, Xi, l, res);
+}
+
 // the right-hand sides and outputs of bk_fold_linsolve / bk_hopf_linsolve (`what`)
 int minaug_check_rhs(bk_ctx* ctx, const char* what, int nrhs, const double* const* rhsu, double* const* dX) {
     if (nrhs < 1 || nrhs > 2) return set_error(ctx, "%s: 1 or 2 right-hand sides (got %d)", what, nrhs);

@@ -316,6 +316,21 @@ int prec_op_create(bk_ctx* ctx, bk_op* J, bk_precond* pl, double a0, double a1, 
 int bls_matrixfree_pl(bk_ctx* ctx, bk_op* J, int m, const double* const* a, const double* const* b, double bscale, const double* c,
                       const double* rhst, const double* rhsb, bool has_shift, double shift, const bk_gmres_opts& ls, bk_precond* pl,
                       double* u1, double* u2, GmresResult* res, const double* const* atil = nullptr);
+// The real-equivalent operator of a complex-shift solve on stacked (re, im) vectors of length 2 J->n, for operators built on top of
+// it (cshift.hip: ComplexShiftOp; delete `*out` after the solve).  order 0: a0 + a1 Pl^-1 J, order 1: Pl^-1 (a0 + a1 J); tmp: J->n
+// doubles owned by the caller.
+int cshift_op_create(bk_ctx* ctx, bk_op* J, bk_precond* pl, double a0r, double a0i, double a1, int order, double* tmp, bk_op** out);
+// y += xi atil, d = b^H x on (re, im) pairs of length n (bordered.hip: cbordered_tail_kernel); coef = (Re xi, Im xi), dots = (Re d,
+// Im d); yr, yi must not alias each other or any other operand
+int cbordered_tail(bk_ctx* ctx, size_t n, double* yr, double* yi, const double* xr, const double* xi, const double* atr,
+                   const double* ati, const double* br, const double* bi, const double* coef, double* dots);
+// MatrixFreeBLS with the left preconditioner diag(Pl, 1) and a complex shift on (re, im) pairs (bordered.hip): ONE real GMRES on the
+// real-equivalent (2N + 2) system of
+//     diag(Pl^-1, 1) [shift + J, a; bscale b^H, c] [u1; u2] = [Pl^-1 rhst; rhsb],      a, b, rhst, u1: {re, im} (im of a, b, rhst
+// may be NULL = 0), c, rhsb, shift, u2: (re, im) host pairs.
+int bls_matrixfree_pl_cshift(bk_ctx* ctx, bk_op* J, const double* const a[2], const double* const b[2], double bscale, const double c[2],
+                             const double* const rhst[2], const double rhsb[2], const double shift[2], const bk_gmres_opts& ls,
+                             bk_precond* pl, double* u1_re, double* u1_im, double u2[2], GmresResult* res);
 // callback(state; fromNewton) of the Newton correctors (solver.hip, minaug.h): the cbMaxNorm veto, then the user's function;
 // 0 = stop
 int newton_cb(const bk_newton_opts* no, const double* x, const double* fx, double residual, int step, int itlinear, double p,

@@ -766,6 +766,25 @@ class MatrixFreeBLS:
             C.byref(it)), "bk_bls_matrixfree")
         return dX, dl.value, bool(cv.value), it.value
 
+    def solve_complex(self, J, dR, dzu, dzp, R, n, xiu=1.0, xip=1.0, *, shift: complex, dotscale=1.0):
+        """(lbs::MatrixFreeBLS)(J, dR, dzu, dzp, R, n; shift::Complex) on complex data ((re, im) pairs of HipVecs; ``im`` may be
+        None) with ``use_pl = True``: ONE real GMRES on the real-equivalent (2N + 2) system left-preconditioned by diag(Pl, 1)
+        (bk_bls_matrixfree_pl_cshift), regular where shift + J is singular.  Arguments and return shape of
+        BorderingBLS.solve_complex: ((dX_re, dX_im), dl::complex, cv, its), its = (the one GMRES count, 0)."""
+        if not self.use_pl:
+            raise TypeError("MatrixFreeBLS.solve_complex needs use_pl=True (the complex bordered operator is preconditioned)")
+        ctx = R[0].ctx
+        xr, xi = R[0].similar(), R[0].similar()
+        p = lambda v: _ptr(v.t) if v is not None else None
+        dl = (C.c_double * 2)()
+        it, cv = C.c_int(), C.c_int()
+        lo = self.solver._opts()
+        dzp, n, shift = complex(dzp), complex(n), complex(shift)
+        ctx.check(ctx.lib.bk_bls_matrixfree_pl_cshift(
+            ctx.h, J.h, p(dR[0]), p(dR[1]), p(dzu[0]), p(dzu[1]), dzp.real, dzp.imag, p(R[0]), p(R[1]), n.real, n.imag,
+            float(xiu), float(xip), shift.real, shift.imag, float(dotscale), C.byref(lo), self._need_pl(), p(xr), p(xi),
+            dl, C.byref(cv), C.byref(it)), "bk_bls_matrixfree_pl_cshift")
+        return (xr, xi), complex(dl[0], dl[1]), bool(cv.value), (it.value, 0)
 
     def solve_block(self, J, a, b, c, rhst, rhsb, *, shift=None, dotscale=1.0):
         """solve_bls_block(lbs::MatrixFreeBLS, J, a, b, c, rhst, rhsb; shift, dotp) -> (u1, u2, cv, it),

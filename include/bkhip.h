@@ -426,6 +426,26 @@ int bk_bls_bordering_cshift(bk_ctx* ctx, bk_op* J, const double* dR_re, const do
                             double xip, double shift_re, double shift_im, double dotscale,
                             const bk_gmres_opts* lsopts, bk_precond* pl, double* dX_re, double* dX_im,
                             double dl[2], int* converged, int itlinear[2]);
+/* MatrixFreeBLS (src/LinearBorderSolver.jl:326-352, :424-437) for the same arguments with the solver's LEFT preconditioner carried
+ * into the bordered system as diag(Pl, 1): the complex counterpart of bk_bls_matrixfree_pl.  ONE real GMRES on the real-equivalent
+ * (2N + 2) system of
+ *     out.u = Pl^-1 ((shift + J) x.u) + x.p (Pl^-1 dR) ,   out.p = dzp xip x.p + xiu dotscale dzu^H x.u
+ * with the right-hand side (Pl^-1 R, n); Pl^-1 acts on each half, the shift sits under Pl^-1 in every GMRES flavor.  Regular where
+ * shift + J is singular (the bordered systems of src/codim2/MinAugHopf.jl:17, 72-76 at a Hopf point).  One itlinear.  MINRES / CG
+ * flavors, a right preconditioner, a missing pl, an odd local length and ranks > 1 are refused.                              */
+int bk_bls_matrixfree_pl_cshift(bk_ctx* ctx, bk_op* J, const double* dR_re, const double* dR_im,
+                                const double* dzu_re, const double* dzu_im, double dzp_re, double dzp_im,
+                                const double* R_re, const double* R_im, double n_re, double n_im, double xiu,
+                                double xip, double shift_re, double shift_im, double dotscale,
+                                const bk_gmres_opts* lsopts, bk_precond* pl, double* dX_re, double* dX_im,
+                                double dl[2], int* converged, int* itlinear);
+/* The per-application pass of that operator, exposed for exact tests: on (re, im) pairs of length n, y += xi at in place with
+ * xi = coef[0] + i coef[1] (every product and sum rounded on its own, y_re + xi_r at_re - xi_i at_im, y_im + xi_r at_im + xi_i at_re)
+ * and dots = b^H x = (b_re.x_re + b_im.x_im, b_re.x_im - b_im.x_re) (four deterministic two-stage sums, one host read), in ONE pass:
+ * eight read streams, two written, 80 n bytes.  y_re, y_im must not alias each other or another operand.                     */
+int bk_cbordered_tail(bk_ctx* ctx, size_t n, double* y_re, double* y_im, const double* x_re, const double* x_im,
+                      const double* at_re, const double* at_im, const double* b_re, const double* b_im,
+                      const double coef[2], double dots[2]);
 
 /* ------------------------------------------------------------------ continuation step -----------
  * The body of `iterate` (src/Continuation.jl:458-504) as one call: corrector! (newton_palc), compute_eigenvalues!
@@ -588,7 +608,13 @@ int bk_hopf_contract(bk_problem* prob, const double* u, const double* params, in
 /* _compute_bordered_vectors + _get_bordered_terms (MinAugHopf.jl) at (x, params, omega): v, sigma from
  * bk_bls_bordering_cshift(J, a, b, 0, 0, 1; shift = -i omega), w from the same on the adjoint handle with a and b exchanged and
  * shift = +i omega (a_im, b_im may be NULL).  sigma[2], and (each may be NULL) sigma_p[2] = -w^H dJ/dp v and
- * sigma_omega[2] = i w^H v.  itlinear[0] / [1]: GMRES counts of the v / w solves.                                        */
+ * sigma_omega[2] = i w^H v.  itlinear[0] / [1]: GMRES counts of the v / w solves.
+ * Context option "hopf_bordered" (default 0, read once per call by bk_hopf_terms, bk_newton_hopf and bk_bautin_normal_form; no
+ * option struct changes).  J - i omega is singular at a Hopf point, where the two shifted solves of each BEC pass stop unconverged.
+ * At 1, (v, sigma) and w each come from ONE solve of their bordered system, which is regular there, with
+ * bk_bls_matrixfree_pl_cshift (pl must be given); itlinear[0] / [1] = the two GMRES counts, "hopf_unconverged_solves" counts as
+ * before.  The Newton step (bk_hopf_linsolve) stays by elimination: J itself is regular at a Hopf point, and the reference
+ * eliminates there too (MinAugHopf.jl:160-197).  The H21 solve of bk_bautin_normal_form goes the same way.                  */
 int bk_hopf_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar, double omega,
                   const double* a_re, const double* a_im, const double* b_re, const double* b_im, const bk_gmres_opts* lsopts,
                   bk_precond* pl, double* v_re, double* v_im, double* w_re, double* w_im, double sigma[2], double sigma_p[2],
