@@ -1,5 +1,5 @@
 // Streaming scaffolding of the HBM-bound kernels: 256-thread workgroups, 16-byte loads per lane, the contiguous-burst grid-stride
-// walk and the wave64 sum (vecops.hip), and on top of them the two generic passes of fold.hip, hopf.hip, hopf_nf.hip, bautin.hip and nf1d.hip.
+// walk and the wave64 sum (vecops.hip), and on top of them the two generic passes of fold.hip, hopf.hip, hopf_nf.hip, bautin.hip, nf1d.hip and nfnd.hip.
 //
 // How to add a streaming pass: write a plain struct with `static constexpr int NIN, U, FIELDS` (read streams; 16-byte items per
 // lane in flight; streams per vector: 2 when the stacked cGL fields p, p + n are walked side by side over n points, x[2 k + f] =

@@ -772,6 +772,48 @@ int bk_normal_form_1d(bk_ctx* ctx, bk_problem* prob, const double* x, const doub
                       const double* zeta, const double* zeta_star, const bk_bordering_opts* bopts, const bk_gmres_opts* lsopts,
                       bk_precond* pl, double* psi01, double* psi20, double coef[5], int* converged, int itlinear[3]);
 
+/* ------------------------------------------------------------------ normal form, 2-d and 3-d kernels -------------
+ * get_normal_formNd (src/NormalForms.jl:648-896), matrix-free, for BK_PDE_SH (2-D / 3-D) and BK_PDE_SH1D (any other problem:
+ * the error of the fold entries above) at a branch point (x, params) whose kernel has dimension N = 2 or 3.  J' = J, the
+ * is_symmetric branch (:741-743): zeta*_i = zeta_i, and the N kernel vectors zeta[0..N) come orthonormal in l2 (what
+ * biorthogonalise, :752, leaves).  With E(r) = r - sum_i <r, zeta_i> zeta_i and the bordered matrix B = [J Z; Z' 0],
+ * Z = (zeta_0 ... zeta_{N-1}):
+ *   a01[i]        = <dpF, zeta_i>                                         B [Psi01; s] = [E(-dpF); 0]                    (:783, :798)
+ *   b20[i,(j,k)]  = <d2F[zeta_j, zeta_k], zeta_i>            j <= k        B [Psijk; s] = [E(-d2F[zeta_j, zeta_k]); 0]    (:822-826, :844-857)
+ *   b11[i,j]      = <dJ/dp zeta_j + d2F[zeta_j, Psi01], zeta_i>                                                          (:800-803)
+ *   a02[i]        = <2 dJ/dp Psi01 + d2F[Psi01, Psi01], zeta_i>                                                          (:812-813)
+ *   b30[i,(j,k,l)]= <d3F[zeta_j, zeta_k, zeta_l] + d2F[zeta_j, Psikl] + d2F[zeta_k, Psijl] + d2F[zeta_l, Psijk], zeta_i>,  j <= k <= l  (:842-871)
+ * in a01 dp + a02 dp^2 / 2 + b11 x dp + b20 x x / 2 + b30 x x x / 6 (:541-574).  P = N (N + 1) / 2 pairs (j <= k) and T =
+ * N (N + 1) (N + 2) / 6 triples (j <= k <= l), both in lexicographic order; packed layouts a01[i], a02[i], b11[i N + j],
+ * b20[i P + jk], b30[i T + jkl].  The tensors are pointwise and analytic and d2F/dp2 = 0 (the reference: ForwardDiff or central
+ * differences, :771-780); the border has all N columns (the reference: the first two, :759-760); every Psijk is solved once
+ * (the reference re-solves three systems per triple) and a02 is computed once per i.                                         */
+/* One streaming pass over u and the N zeta that writes nothing: host out[N + N P + N N] = (a01 | b20 | <zeta_i, zeta_j>) for
+ * params[ipar] (12 values for N = 2, 30 for N = 3).  Deterministic, all-reduced.                                             */
+int bk_nfnd_dots(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, int N,
+                 const double* const* zeta, double* out);
+/* One pass over u and the N zeta: the 1 + P projected right-hand sides r[0] = E(-dpF) = sum_i a01[i] zeta_i - dpF and
+ * r[1 + jk] = sum_i b20[i P + jk] zeta_i - d2F[zeta_j, zeta_k] (:798, :844-857) with the a01, b20 of bk_nfnd_dots.  The sum
+ * over i runs left to right and every product and sum is rounded on its own.  The outputs are distinct and alias no input.   */
+int bk_nfnd_rhs(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, int N,
+                const double* const* zeta, const double* a01, const double* b20, double* const* r);
+/* One streaming pass over u, the N zeta, Psi01 and the P Psijk (7 streams for N = 2, 11 for N = 3): host
+ * out[N N + N + N T] = (b11 | a02 | b30) for params[ipar] (14 | 42 values).  Deterministic, all-reduced.                    */
+int bk_nfnd_contract(bk_problem* prob, const double* u, const double* params, int nparams, int ipar, int N,
+                     const double* const* zeta, const double* psi01, const double* const* psi2, double* out);
+/* The whole computation at (x, params) for params[ipar]: the pass of bk_nfnd_dots, the pass of bk_nfnd_rhs, 1 + P solves as
+ * bk_bls_block_matrixfree_pl (m = N, a = b = zeta, c = 0, bottom right-hand side 0; Pl^-1 zeta_j is formed once for all of
+ * them) and the pass of bk_nfnd_contract.  Errors: N outside {2, 3}; a problem without the fold formulation; pl == NULL; an
+ * output (psi01, psi2[0..P)) that aliases another output, x or a zeta; |<zeta_i, zeta_j> - delta_ij| > 1e-8.
+ * coef[2 N + N N + N P + N T] = [a01 | a02 | b11 | b20 | b30] (22 values for N = 2, 63 for N = 3); itlinear[1 + P] = GMRES
+ * counts of the Psi01 and Psijk solves.  The bordered system is regular at the point itself; an unconverged solve is still a
+ * flag and no error (the reference logs it, :799, :846): *converged = the AND over all solves, and each unconverged one adds 1
+ * to the context counter "nfnd_unconverged_solves".  The predictor vectors x0 + sum_i x_i zeta_i (:576-582) are
+ * bk_nf1d_predict with zeta_0, zeta_1, zeta_2 in its (zeta, psi01, tau) slots.                                               */
+int bk_normal_form_nd(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar, int N,
+                      const double* const* zeta, const bk_gmres_opts* lsopts, bk_precond* pl, double* psi01,
+                      double* const* psi2, double* coef, int* converged, int* itlinear);
+
 #ifdef __cplusplus
 }
 #endif
