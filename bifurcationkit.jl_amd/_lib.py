@@ -59,6 +59,11 @@ class NewtonResult(C.Structure):
                 ("residuals", C.c_double * (BK_MAX_NEWTON_ITER + 1))]
 
 
+class DeflatedResult(C.Structure):
+    _fields_ = [("converged", C.c_int), ("itnewton", C.c_int), ("itlinear", C.c_int),
+                ("residuals", C.c_double * (BK_MAX_NEWTON_ITER + 1)), ("M", C.c_double), ("min_dist", C.c_double)]
+
+
 BK_MAX_NEV = 62
 
 
@@ -185,6 +190,9 @@ SIGNATURES = {
     "bk_cont_locate_bifurcation": (I, [VP, C.POINTER(BisectionOpts), C.POINTER(BisectionResult)]),
     "bk_newton_deflated": (I, [VP, VP, VP, c_double_p, I, C.POINTER(VP), I, D, D, I, D, C.POINTER(NewtonOpts),
                                C.POINTER(GmresOpts), VP, C.POINTER(NewtonResult)]),
+    "bk_deflation_dots": (I, [VP, SZ, VP, VP, C.POINTER(VP), I, c_double_p, c_double_p]),
+    "bk_newton_deflated_exact": (I, [VP, VP, VP, c_double_p, I, C.POINTER(VP), I, D, D, I, I, C.POINTER(NewtonOpts),
+                                     C.POINTER(GmresOpts), VP, C.POINTER(DeflatedResult)]),
     "bk_newton_palc": (I, [VP, VP, VP, c_double_p, VP, D, VP, D, D, D, c_double_p, I, I, D, D,
                            C.POINTER(NewtonOpts), C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP,
                            C.POINTER(NewtonResult)]),

@@ -1052,12 +1052,17 @@ def newton_palc_native(prob: _PdeProblem, z0: BorderedArray, tau: BorderedArray,
 class DeflationOperator:
     """DeflationOperator(power, dot = VI.inner, alpha, roots; accumulator) of src/DeflationOperator.jl:61-141 on device
     vectors: ``M(u) = prod_i(<u - root_i, u - root_i>^-power + alpha)`` (or the mean), ``dM`` by finite differences
-    (autodiff = false, delta = 1e-8, :160-169)."""
+    (autodiff = false, delta = 1e-8, :160-169).
+
+    ``autodiff = True`` is the reference's exact derivative (:159-169 differentiated): ``__call__`` and ``dM`` run one pass per 8
+    roots (bk_deflation_dots: d_i = <u - r_i, u - r_i>, e_i = <u - r_i, du>) and form, with m_i = d_i^-power + alpha,
+    M = prod_i m_i and dM . du = sum_i (prod_{j != i} m_j) (-2 power d_i^(-power - 1)) e_i (the mean: both sums over k)."""
     power: float
     alpha: float
     roots: list = field(default_factory=list)
     accumulator: str = "prod"
     delta: float = 1e-8
+    autodiff: bool = False
 
     def push(self, v):
         self.roots.append(v)
@@ -1065,9 +1070,47 @@ class DeflationOperator:
     def __len__(self):
         return len(self.roots)
 
+    def dots(self, u: HipVec, du: HipVec = None):
+        """(d, e) of bk_deflation_dots; e is None without ``du``."""
+        k = len(self.roots)
+        ctx = u.ctx
+        rp = (C.c_void_p * max(k, 1))(*[r.t.data_ptr() for r in self.roots])
+        d = (C.c_double * max(k, 1))()
+        e = (C.c_double * max(k, 1))() if du is not None else None
+        ctx.check(ctx.lib.bk_deflation_dots(ctx.h, u.n, _ptr(u.t), _ptr(du.t) if du is not None else None, rp, k, d, e),
+                  "bk_deflation_dots")
+        return [d[i] for i in range(k)], (None if e is None else [e[i] for i in range(k)])
+
+    def combine(self, d, e=None):
+        """(M, dM . du) from the sums, in the library's order: products left to right, prod_{j != i} as prefix times suffix."""
+        k = len(d)
+        if k == 0:
+            return 1.0, 0.0
+        mean = self.accumulator == "mean"
+        power = float(self.power)
+        inv = lambda x, q: math.inf if x == 0.0 else x ** q                      # pow(0, negative) = inf, as in C
+        m = [(math.inf if di == 0.0 else 1.0 / di ** power) + self.alpha for di in d]
+        acc = m[0]
+        for mi in m[1:]:
+            acc = acc + mi if mean else acc * mi
+        M = acc / k if mean else acc
+        if e is None:
+            return M, None
+        suf = [1.0] * (k + 1)
+        for i in range(k - 1, -1, -1):
+            suf[i] = m[i] * suf[i + 1]
+        pre, s = 1.0, 0.0
+        for i in range(k):
+            g = (-2.0 * power * inv(d[i], -power - 1.0)) * e[i]
+            s += g if mean else (pre * suf[i + 1]) * g
+            pre *= m[i]
+        return M, (s / k if mean else s)
+
     def __call__(self, u: HipVec) -> float:
         if not self.roots:
             return 1.0
+        if self.autodiff:
+            return self.combine(self.dots(u)[0])[0]
         out = None
         for r in self.roots:
             d = u.copy().add_(r, -1.0)
@@ -1078,6 +1121,8 @@ class DeflationOperator:
     def dM(self, u: HipVec, du: HipVec) -> float:
         if not self.roots:
             return 0.0
+        if self.autodiff:
+            return self.combine(*self.dots(u, du))[1]
         return (self(u.copy().add_(du, self.delta)) - self(u)) / self.delta
 
 
@@ -1097,8 +1142,42 @@ def deflated_custom_ls(ls, prob, defop: DeflationOperator, u: HipVec, p, rhs: Hi
     return h1.add_(h2, -z).scale_(1.0 / Mu), True, (it1, it2)
 
 
-def newton_deflated(prob, defop: DeflationOperator, x0: HipVec, p, ls, tol=1e-12, max_iterations=25, norm_inf=False):
-    """solve(prob, defOp, options, DeflatedProblemCustomLS()) (:340-355) driven call by call through the plugin surface."""
+def _newton_deflated_exact(prob, defop, x0, p, ls, tol, max_iterations, norm_inf, stop_plain):
+    """bk_newton_deflated_exact call by call: one solve h2 = J^-1 F per step, x <- x - M / (M + dM . h2) h2; stops on |M| |F|
+    (``stop_plain`` False, the reference's rule) or on |F|."""
+    nrm = (lambda v: v.norminf()) if norm_inf else (lambda v: v.norm())
+    x = x0.copy()
+
+    def residual():
+        fx = prob.residual(x, p)
+        d, _ = defop.dots(x)
+        M = defop.combine(d)[0]
+        rf = nrm(fx)
+        return fx, d, M, (rf if stop_plain else abs(M) * rf)
+
+    fx, d, M, r = residual()
+    res = [r]
+    step, itlin = 0, 0
+    while step < max_iterations and math.isfinite(M) and r > tol:
+        h2, _, it = ls(prob.jacobian(x, p), fx)
+        itlin += int(it)
+        e = defop.combine(*defop.dots(x, h2))[1] if defop.roots else 0.0
+        x.add_(h2, -(M / (M + e)))
+        fx, d, M, r = residual()
+        res.append(r)
+        step += 1
+    return dict(u=x, converged=bool(math.isfinite(M) and res[-1] < tol), itnewton=step, itlineartot=itlin, residuals=res, M=M,
+                min_dist=math.sqrt(min(d)) if d else math.inf)
+
+
+def newton_deflated(prob, defop: DeflationOperator, x0: HipVec, p, ls, tol=1e-12, max_iterations=25, norm_inf=False,
+                    stop_plain=False):
+    """solve(prob, defOp, options, DeflatedProblemCustomLS()) (:340-355) driven call by call through the plugin surface.  With
+    ``defop.autodiff`` the one-solve step of bk_newton_deflated_exact, which alone knows ``stop_plain`` (stop on |F|, not |M F|)."""
+    if defop.autodiff:
+        return _newton_deflated_exact(prob, defop, x0, p, ls, tol, max_iterations, norm_inf, stop_plain)
+    if stop_plain:
+        raise ValueError("newton_deflated: stop_plain needs DeflationOperator(..., autodiff=True)")
     nrm = (lambda v: v.norminf()) if norm_inf else (lambda v: v.norm())
     x = x0.copy()
     fx = prob.residual(x, p).scale_(defop(x))
@@ -1115,17 +1194,28 @@ def newton_deflated(prob, defop: DeflationOperator, x0: HipVec, p, ls, tol=1e-12
 
 
 def newton_deflated_native(prob: _PdeProblem, defop: DeflationOperator, x0: HipVec, p: float, ls: _GMRES, tol=1e-12,
-                           max_iterations=25, norm_inf=False):
-    """The same as one library call (bk_newton_deflated)."""
+                           max_iterations=25, norm_inf=False, stop_plain=False):
+    """The same as one library call (bk_newton_deflated; with ``defop.autodiff`` bk_newton_deflated_exact, whose result also
+    carries the final M and the smallest distance to a root)."""
     ctx = prob.ctx
     x = x0.copy()
     pv = prob._pvec(p)
     arr = (C.c_double * len(pv))(*pv)
     no = newton_opts(tol, max_iterations, norm_inf)
     lo = ls._opts()
-    res = L.NewtonResult()
     m = len(defop)
     rp = (C.c_void_p * max(m, 1))(*[r.t.data_ptr() for r in defop.roots])
+    if defop.autodiff:
+        rx = L.DeflatedResult()
+        ctx.check(ctx.lib.bk_newton_deflated_exact(ctx.h, prob.h, _ptr(x.t), arr, len(pv), rp, m, float(defop.power),
+                                                   float(defop.alpha), 1 if defop.accumulator == "mean" else 0,
+                                                   1 if stop_plain else 0, C.byref(no), C.byref(lo), ls._pl(), C.byref(rx)),
+                  "bk_newton_deflated_exact")
+        return dict(u=x, converged=bool(rx.converged), itnewton=rx.itnewton, itlineartot=rx.itlinear,
+                    residuals=[rx.residuals[i] for i in range(rx.itnewton + 1)], M=rx.M, min_dist=rx.min_dist)
+    if stop_plain:
+        raise ValueError("newton_deflated_native: stop_plain needs DeflationOperator(..., autodiff=True)")
+    res = L.NewtonResult()
     ctx.check(ctx.lib.bk_newton_deflated(ctx.h, prob.h, _ptr(x.t), arr, len(pv), rp, m, float(defop.power),
                                          float(defop.alpha), 1 if defop.accumulator == "mean" else 0,
                                          float(defop.delta), C.byref(no), C.byref(lo), ls._pl(), C.byref(res)),

@@ -9,6 +9,8 @@
   get_normal_form_nd       for a point of type "nd" of a native branch
   predictor                the zeros of the reduced equation on both sides of the point, deflated Newton on the host
   predicted_states         x0 + sum_i x_i zeta_i for a list of zeros (bk_nf1d_predict)
+  get_first_points_on_branch   the predicted zeros turned into zeros of F on both sides, deflated Newton with the exact dM
+  multicontinuation        normal form -> predictor -> first points -> one branch per state found
 
 J' = J, the reference's is_symmetric branch: zeta*_i = zeta_i, and biorthogonalise reduces to orthonormalising the kernel basis
 zeta_0 .. zeta_{N-1}.  With E(r) = r - sum_i <r, zeta_i> zeta_i and B = [J Z; Z' 0], Z = (zeta_0 ... zeta_{N-1}):
@@ -35,13 +37,15 @@ from __future__ import annotations
 import ctypes as C
 import itertools
 import math
-from dataclasses import dataclass
+import warnings
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
+from . import continuation as Cn
 from .codim2 import _carr, _saved, _vptrs
-from .hip import HipVec, MatrixFreeBLS, _GMRES, _ptr
-from .normal_form1d import TOL_FOLD, _tangent, is_sh_problem, nf1d_predict
+from .hip import DeflationOperator, HipVec, MatrixFreeBLS, _GMRES, _ptr, newton_deflated_native, newton_native
+from .normal_form1d import TOL_FOLD, Branch, _tangent, is_sh_problem, nf1d_predict
 
 
 def pairs(N: int):
@@ -383,3 +387,134 @@ def predicted_states(bp: NdBranchPoint, roots):
     for k in range(0, len(coefs), 4):
         out.extend(nf1d_predict(bp.x0, z[0], z[1], z[2], coefs[k:k + 4]))
     return out
+
+
+# ------------------------------------------------------------------------------------------ multicontinuation
+@dataclass
+class FirstPoints:
+    """What get_first_points_on_branch returns (the reference's named tuple, :351, plus the bookkeeping): ``before`` / ``after`` are
+    the DeflationOperators of the two sides, roots[0] a copy of bp.x0 and roots[1:] the states found at ``bpm`` = bp.p - |dp| /
+    ``bpp`` = bp.p + |dp|; ``records`` has one dict per predicted zero: side, index, zero, status ("found" | "lost" | "trivial" |
+    "duplicate"), itnewton, itlinear, residual (final, of the quantity stopped on) and min_dist (smallest distance to the roots held when
+    the zero was tried; None for "trivial")."""
+    before: DeflationOperator
+    after: DeflationOperator
+    bpm: float
+    bpp: float
+    records: list = field(default_factory=list)
+
+    def count(self, side: str, status: str) -> int:
+        return sum(1 for r in self.records if r["side"] == side and r["status"] == status)
+
+
+def get_first_points_on_branch(bp: NdBranchPoint, roots, prob, ls, nopt, delta_p, usedeflation=True, max_iter_deflation=None,
+                               perturb_guess=None, normC=Cn.norm2, stop_plain=True, solver=None) -> FirstPoints:
+    """get_first_points_on_branch (src/bifdiagram/BranchSwitching.jl:298-352): the zeros ``roots`` = {"before": [...], "after":
+    [...]} of the reduced equation (predictor) turned into zeros of F.  Each side has its own DeflationOperator(2, 1, [copy of
+    x0], autodiff=True) (:325, :339) and walks its zeros in order: deflated Newton (bk_newton_deflated_exact; plain bk_newton
+    with usedeflation = False) from perturb_guess(bp(x, dp)) at bp.p -+ |delta_p| with ``nopt``'s tolerance, ``max_iter_deflation``
+    (default min(50, 15 nopt.max_iterations), :304) iterations and the norm ``normC``; what converges is pushed (:335, :348).
+    ``solver`` (default hip.newton_deflated_native) is called as solver(prob, defop, x, p, ls, tol=, max_iterations=, norm_inf=,
+    stop_plain=) and returns a dict with u, converged, itnewton, residuals, min_dist.
+
+    Deviations from the reference:
+      stop_plain = True   Newton stops on |F| < tol, not on |M F| < tol.  With the roots of a multicontinuation 0.2 - 0.4 apart
+          M = prod (d_i^-2 + 1) ~ 1e5, and the reference's rule asks |F| < 1e-15, below the rounding floor of F: starts that sit
+          on their zero never "converge".  Measured with the dense restatement (tests/multicontinuation_ref.py; 16 x 16 SH,
+          half-lengths (pi, pi), modes (1,2), (2,1), nu = 1.3, tol 1e-10): the reference's rule finds 6 of the 8 states at
+          dp = 0.008 and 2 of 8 at 0.004, the plain rule 8 of 8 at dp = 0.008 .. 0.001 in 4 - 12 iterations; 8 x 8 x 8,
+          half-lengths 2.5, nu = 0.9: 26 of 26 at dp = 1e-4.  |F| < tol follows from |M F| < tol whenever alpha >= 1, so the plain
+          rule only accepts more.  stop_plain = False is the reference's rule.
+      duplicates          with the plain rule a state may converge onto a root already held (M is finite next to it): a state
+          within 1e-6 (1 + |x|_2) of a held root is recorded as "duplicate" and not pushed.
+      nothing is printed; the zero at the origin is recorded as "trivial" and not tried (the reference starts Newton on x0 with x0
+          deflated, which cannot converge); lost zeros are named by one warning per side."""
+    dp = abs(float(delta_p))
+    nmax = max_iter_deflation if max_iter_deflation is not None else min(50, 15 * nopt.max_iterations)
+    if normC not in (Cn.norm2, Cn.norminf):
+        raise TypeError("get_first_points_on_branch: normC must be norm2 or norminf")
+    inf = normC is Cn.norminf
+    if solver is None:
+        solver = newton_deflated_native
+    records = []
+
+    def side(name, zeros, sgn):
+        defop = DeflationOperator(2, 1.0, [bp.x0.copy()], autodiff=True)
+        p = bp.p + sgn * dp
+        for k, z in enumerate(zeros):
+            z = np.asarray(z, dtype=float)
+            rec = dict(side=name, index=k, zero=z, status="trivial", itnewton=0, itlinear=0, residual=None, min_dist=None)
+            records.append(rec)
+            if not np.abs(z).max() > 0:
+                continue
+            x = bp(z, sgn * dp)
+            if perturb_guess is not None:
+                x = perturb_guess(x)
+            if usedeflation:
+                sol = solver(prob, defop, x, p, ls, tol=nopt.tol, max_iterations=nmax, norm_inf=inf, stop_plain=stop_plain)
+                dmin = sol["min_dist"]
+            else:
+                sol = newton_native(prob, x, p, ls, tol=nopt.tol, max_iterations=nmax, norm_inf=inf)
+                dmin = math.sqrt(min(defop.dots(sol["u"])[0]))
+            rec.update(itnewton=sol["itnewton"], itlinear=sol.get("itlineartot"), residual=sol["residuals"][-1], min_dist=dmin)
+            if not sol["converged"]:
+                rec["status"] = "lost"
+            elif not dmin > 1e-6 * (1.0 + sol["u"].norm()):
+                rec["status"] = "duplicate"
+            else:
+                rec["status"] = "found"
+                defop.push(sol["u"])
+        lost = sum(1 for r in records if r["side"] == name and r["status"] == "lost")
+        if lost:
+            warnings.warn(f"get_first_points_on_branch: {lost} of the {len(zeros)} predicted zeros {name} the bifurcation point "
+                          "did not converge (status \"lost\")")
+        return defop
+
+    after = side("after", roots["after"], 1.0)              # the reference's order: after, then before
+    before = side("before", roots["before"], -1.0)
+    return FirstPoints(before=before, after=after, bpm=bp.p - dp, bpp=bp.p + dp, records=records)
+
+
+def multicontinuation(br, ind, prob, alg: Cn.PALC, cp: Cn.ContinuationPar, delta_p=None, ampfactor=1.0, predictor_kwargs=None,
+                      first_points: FirstPoints = None, roots=None, usedeflation=True, max_iter_deflation=None, perturb_guess=None,
+                      stop_plain=True, eig=None, nev=None, zetas=None, tol_fold=TOL_FOLD, normC=Cn.norm2, verbosity=0,
+                      save_sol=False, bisection=False, finalise_solution=None, callback_newton=None, filename=None):
+    """multicontinuation (src/bifdiagram/BranchSwitching.jl:234-291, 355-442) at a point of type "nd" of a native branch: every
+    branch that leaves it.  ``ind``: the index of the special point (the normal form is computed: get_normal_form_nd with ``eig``,
+    default the eigensolver of cp.newton_options, ``nev`` and ``zetas``) or an NdBranchPoint.  Then predictor(bp, |dp|,
+    ampfactor, **predictor_kwargs) unless ``roots`` is given, get_first_points_on_branch unless ``first_points`` is given -- the
+    stages are decoupled as the reference advises for large problems (:231-232) -- and one branch per root from the second on
+    (the first is the trivial state, :396): from (bp.x0, bp.p) to (root, bp.p -+ |dp|) with ds = -+|cp.ds| (:432-435), every step
+    one library call as in continuation_native.  dp = delta_p, default cp.ds (:413).  Returns ([normal_form1d.Branch(branch, bp)
+    for the roots before, then after], FirstPoints).
+
+    Deviations from the reference: the first points stop on |F| (``stop_plain`` = True) and drop duplicates, both stated with
+    their measurements in get_first_points_on_branch; nothing is printed."""
+    if normC not in (Cn.norm2, Cn.norminf):
+        raise TypeError("multicontinuation: normC must be norm2 or norminf")
+    nopt = cp.newton_options
+    ls = nopt.linsolver
+    if isinstance(ind, NdBranchPoint):
+        bp = ind
+    else:
+        bp = get_normal_form_nd(br, ind, prob, ls, eig=eig if eig is not None else nopt.eigsolver,
+                                nev=nev if nev is not None else cp.nev, zetas=zetas, tol_fold=tol_fold)
+    dp = abs(float(cp.ds if delta_p is None else delta_p))
+    if first_points is None:
+        if roots is None:
+            roots = predictor(bp, dp, ampfactor=ampfactor, **(predictor_kwargs or {}))
+        first_points = get_first_points_on_branch(bp, roots, prob, ls, nopt, dp, usedeflation=usedeflation,
+                                                  max_iter_deflation=max_iter_deflation, perturb_guess=perturb_guess, normC=normC,
+                                                  stop_plain=stop_plain)
+    inf = normC is Cn.norminf
+    dscont = abs(cp.ds)
+    first = lambda x: dict(u=x, itnewton=0, itlineartot=0, residuals=[])
+
+    def run(sol, p1, ds):
+        cp2 = replace(cp, ds=ds)
+        return Cn._continuation_native_from(prob, first(bp.x0), float(bp.p), dict(u=sol), float(p1), alg.update(cp2), cp2, inf,
+                                            verbosity, save_sol, bisection, finalise_solution, callback_newton, None, filename)
+
+    branches = [Branch(run(r, first_points.bpm, -dscont), bp) for r in first_points.before.roots[1:]]
+    branches += [Branch(run(r, first_points.bpp, dscont), bp) for r in first_points.after.roots[1:]]
+    return branches, first_points

@@ -525,6 +525,41 @@ int bk_newton_deflated(bk_ctx* ctx, bk_problem* prob, double* x, const double* p
                        int accumulator_mean, double delta, const bk_newton_opts* nopts,
                        const bk_gmres_opts* lsopts, bk_precond* pl, bk_newton_result* res);
 
+/* ------------------------------------------------------------------ deflation with the exact derivative ---
+ * DeflationOperator(power, dot, alpha, roots; autodiff = true) (src/DeflationOperator.jl:61-169), as multicontinuation uses it
+ * for 9 to 27 deflated states (src/bifdiagram/BranchSwitching.jl:325,339).  With t_i = u - root_i, d_i = <t_i, t_i>,
+ * e_i = <t_i, h> and m_i = d_i^-power + alpha:
+ *   M(u) = prod_i m_i,          dM(u) . h = sum_i (prod_{j != i} m_j) (-2 power d_i^(-power - 1)) e_i        (Val(:Prod), :124-138)
+ *   M(u) = (sum_i m_i) / k,     dM(u) . h = (sum_i (-2 power d_i^(-power - 1)) e_i) / k                      (Val(:Mean))
+ * which is what :159-169 differentiates.                                                                                       */
+/* One streaming pass per 8 roots over u, h and the roots (1 + 1 + 8 streams) that writes nothing: host d[nroots] and
+ * e[nroots].  h == NULL (then e == NULL too): the d_i alone; the d_i are the same sums bit for bit with and without h.  A root
+ * equal to u gives d_i = 0 exactly.  Deterministic, all-reduced.                                                               */
+int bk_deflation_dots(bk_ctx* ctx, size_t n, const double* u, const double* h /* may be NULL */,
+                      const double* const* roots, int nroots, double* d, double* e /* NULL iff h is */);
+typedef struct {
+    int converged;
+    int itnewton;
+    int itlinear;                                /* one solve per Newton step                                         */
+    double residuals[BK_MAX_NEWTON_ITER + 1];    /* of the quantity stopped on: |M F| or |F|                          */
+    double M;                                    /* M at the final x                                                  */
+    double min_dist;                             /* min_i sqrt(d_i) at the final x, +inf without roots                */
+} bk_deflated_result;
+/* _newton (src/Newton.jl:66-114) on M(u) F(u) with the exact dM and ONE linear solve per step.  DeflatedProblemCustomLS
+ * (src/DeflationOperator.jl:264-312) solves h1 = J^-1 (M F) and h2 = J^-1 F and steps by h = (h1 - z h2) / M,
+ * z = dM.h1 / (M + dM.h2); h1 = M h2 by linearity, so with e = dM(u) . h2 the same step is x <- x - M / (M + e) h2
+ * (Sherman-Morrison on M J + F grad M').  Per step: one GMRES solve and one pass of bk_deflation_dots with h = h2; the residual
+ * evaluation runs the pass without h and its d_i serve the next step.
+ * stop_plain == 0: stop on |M F| = |M| |F| < tol, the reference's rule (:340-355); != 0: stop on |F| < tol, which follows from
+ * the former whenever alpha >= 1 and does not ask |F| to fall below tol / M (~ tol 1e-5 with several roots 0.2 - 0.4 away).
+ * The norm is nopts->norm_inf ? inf : 2; nopts' callback and max_residual are not consulted.
+ * A root with d_i = 0 (x on a deflated state) makes M infinite: converged = 0, no error.  x == roots[i] (aliased) is refused with
+ * a message.  nroots == 0 is plain Newton.                                                                                     */
+int bk_newton_deflated_exact(bk_ctx* ctx, bk_problem* prob, double* x, const double* params, int nparams,
+                             const double* const* roots, int nroots, double power, double alpha,
+                             int accumulator_mean, int stop_plain, const bk_newton_opts* nopts,
+                             const bk_gmres_opts* lsopts, bk_precond* pl, bk_deflated_result* res);
+
 /* ------------------------------------------------------------------ fold points (codim 2) ---------------
  * The minimally augmented fold formulation of src/codim2/MinAugFold.jl, matrix-free (the reference assembles it for MatrixBLS /
  * MinAugMatrixBased): unknowns (x, p = params[ipar]), G(x, p) = (F(x, p), sigma(x, p)) with sigma from
