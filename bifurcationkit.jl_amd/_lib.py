@@ -64,6 +64,12 @@ class DeflatedResult(C.Structure):
                 ("residuals", C.c_double * (BK_MAX_NEWTON_ITER + 1)), ("M", C.c_double), ("min_dist", C.c_double)]
 
 
+class DefContSeekResult(C.Structure):
+    _fields_ = [("converged", C.c_int), ("itnewton", C.c_int), ("itlinear", C.c_int), ("accepted", C.c_int),
+                ("reason", C.c_int), ("itnewton_total", C.c_int), ("M", C.c_double), ("min_dist", C.c_double),
+                ("plain_residual", C.c_double), ("min_dist_normC", C.c_double)]
+
+
 BK_MAX_NEV = 62
 
 
@@ -193,6 +199,10 @@ SIGNATURES = {
     "bk_deflation_dots": (I, [VP, SZ, VP, VP, C.POINTER(VP), I, c_double_p, c_double_p]),
     "bk_newton_deflated_exact": (I, [VP, VP, VP, c_double_p, I, C.POINTER(VP), I, D, D, I, I, C.POINTER(NewtonOpts),
                                      C.POINTER(GmresOpts), VP, C.POINTER(DeflatedResult)]),
+    "bk_deflation_dist": (I, [VP, SZ, VP, C.POINTER(VP), I, c_double_p, c_double_p]),
+    "bk_vec_perturb": (I, [VP, SZ, VP, D, C.c_ulonglong, C.c_ulonglong]),
+    "bk_defcont_seek": (I, [VP, VP, VP, c_double_p, I, C.POINTER(VP), I, D, D, I, I, I, D, I, C.POINTER(GmresOpts), VP,
+                            c_double_p, I, C.POINTER(DefContSeekResult)]),
     "bk_newton_palc": (I, [VP, VP, VP, c_double_p, VP, D, VP, D, D, D, c_double_p, I, I, D, D,
                            C.POINTER(NewtonOpts), C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP,
                            C.POINTER(NewtonResult)]),

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "common.h"
+#include "deflate.h"
 #include "ops.h"
 #include "stream.h"
 
@@ -25,13 +26,11 @@ namespace bk {
 
 namespace {
 
-constexpr int kDeflRoots = 8;   // roots per launch
-
 // s[i] = sum t_i t_i,  s[K + i] = sum t_i h  (D = 1),  t_i = u - r_i formed once per element.  U depends on K alone: the d of
 // the passes with and without h are then the same sums in the same order, bit for bit.
 template <int K, int D>
 struct DeflDots {
-    static constexpr int NIN = 1 + D + K, NV = K * (1 + D), U = K <= 3 ? 2 : 1, FIELDS = 1;
+    static constexpr int NIN = 1 + D + K, NV = K * (1 + D), U = defl_unroll(K), FIELDS = 1;
     static_assert(NV <= kPartialVals, "partial sums per workgroup");
     const double* in[NIN];          // u, h (D = 1), r_0 .. r_{K-1}
     __device__ __forceinline__ void operator()(const double (&x)[NIN], double (&s)[NV]) const {
@@ -96,6 +95,61 @@ void defl_M(const double* d, const double* e, int k, double power, double alpha,
 }
 
 }  // namespace
+
+int defl_newton(bk_ctx* ctx, bk_problem* prob, double* x, const double* params, int nparams, const double* const* roots, int nroots,
+                double power, double alpha, int accumulator_mean, int stop_plain, int norm_inf, double tol, int max_iterations,
+                const bk_gmres_opts* lsopts, bk_precond* pl, double* hist, int cap, DeflNewton* out) {
+    const size_t n = prob->nloc;
+    WsGuard ws(ctx);
+    double *fx = nullptr, *h2 = nullptr;
+    BK_TRY(ws.get(n, &fx));
+    BK_TRY(ws.get(n, &h2));
+    std::vector<double> d(nroots), e(nroots);
+    const bool inf = norm_inf != 0;
+    double M = 1.0, r = 0.0, rf = 0.0;
+    // F(x), the d_i and M(x); r = |M| |F| (the reference's rule: |M F| needs no vector) or |F|
+    auto residual = [&]() -> int {
+        BK_TRY(bk_residual(prob, x, params, nparams, fx));
+        BK_TRY(v_deflation_dots(ctx, n, x, nullptr, roots, nroots, d.data(), nullptr));
+        defl_M(d.data(), nullptr, nroots, power, alpha, accumulator_mean, &M, nullptr);
+        BK_TRY(inf ? v_nrminf(ctx, n, fx, &rf) : v_nrm2(ctx, n, fx, &rf));
+        r = stop_plain ? rf : std::fabs(M) * rf;
+        return 0;
+    };
+    BK_TRY(residual());
+    int step = 0, itlin = 0;
+    hist[0] = r;
+    // a root on x: M is infinite, not converged (with stop_plain the plain residual there is small -- x is a deflated state)
+    while (step < max_iterations && std::isfinite(M) && r > tol) {
+        bk_op* J = nullptr;
+        BK_TRY(bk_jacobian(prob, x, params, nparams, &J));
+        GmresResult g;
+        const int s = linsolve(ctx, J, fx, h2, 0.0, 1.0, *lsopts, pl, &g);           // h2 = J^-1 F; h1 = M h2
+        bk_op_destroy(J);
+        if (s != 0) return s;
+        itlin += g.niter;
+        double dMh = 0.0, Mx;
+        if (nroots > 0) {
+            // e_i at the same x: its d_i are the sums of the residual evaluation again, bit for bit
+            BK_TRY(v_deflation_dots(ctx, n, x, h2, roots, nroots, d.data(), e.data()));
+            defl_M(d.data(), e.data(), nroots, power, alpha, accumulator_mean, &Mx, &dMh);
+        }
+        BK_TRY(v_axpby(ctx, n, -(M / (M + dMh)), h2, 1.0, x));
+        BK_TRY(residual());
+        step += 1;
+        hist[step % cap] = r;
+    }
+    out->converged = std::isfinite(M) && r < tol;
+    out->itnewton = step;
+    out->itlinear = itlin;
+    out->M = M;
+    double dmin = HUGE_VAL;
+    for (int i = 0; i < nroots; ++i) dmin = d[i] < dmin ? d[i] : dmin;
+    out->min_dist = nroots > 0 ? std::sqrt(dmin) : HUGE_VAL;
+    out->plain_residual = rf;
+    return 0;
+}
+
 }  // namespace bk
 
 using namespace bk;
@@ -121,54 +175,14 @@ int bk_newton_deflated_exact(bk_ctx* ctx, bk_problem* prob, double* x, const dou
         if (!roots[i]) return -1;
         if (roots[i] == x) return set_error(ctx, "bk_newton_deflated_exact: x aliases root %d (the iterate is updated in place)", i);
     }
-    const size_t n = prob->nloc;
-    WsGuard ws(ctx);
-    double *fx = nullptr, *h2 = nullptr;
-    BK_TRY(ws.get(n, &fx));
-    BK_TRY(ws.get(n, &h2));
-    std::vector<double> d(nroots), e(nroots);
-    const bool inf = no->norm_inf != 0;
-    double M = 1.0, r = 0.0;
-    // F(x), the d_i and M(x); r = |M| |F| (the reference's rule: |M F| needs no vector) or |F|
-    auto residual = [&]() -> int {
-        BK_TRY(bk_residual(prob, x, params, nparams, fx));
-        BK_TRY(v_deflation_dots(ctx, n, x, nullptr, roots, nroots, d.data(), nullptr));
-        defl_M(d.data(), nullptr, nroots, power, alpha, accumulator_mean, &M, nullptr);
-        double rf;
-        BK_TRY(inf ? v_nrminf(ctx, n, fx, &rf) : v_nrm2(ctx, n, fx, &rf));
-        r = stop_plain ? rf : std::fabs(M) * rf;
-        return 0;
-    };
-    BK_TRY(residual());
-    int step = 0, itlin = 0;
-    res->residuals[0] = r;
-    // a root on x: M is infinite, not converged (with stop_plain the plain residual there is small -- x is a deflated state)
-    while (step < no->max_iterations && std::isfinite(M) && r > no->tol) {
-        bk_op* J = nullptr;
-        BK_TRY(bk_jacobian(prob, x, params, nparams, &J));
-        GmresResult g;
-        const int s = linsolve(ctx, J, fx, h2, 0.0, 1.0, *lsopts, pl, &g);           // h2 = J^-1 F; h1 = M h2
-        bk_op_destroy(J);
-        if (s != 0) return s;
-        itlin += g.niter;
-        double dMh = 0.0, Mx;
-        if (nroots > 0) {
-            // e_i at the same x: its d_i are the sums of the residual evaluation again, bit for bit
-            BK_TRY(v_deflation_dots(ctx, n, x, h2, roots, nroots, d.data(), e.data()));
-            defl_M(d.data(), e.data(), nroots, power, alpha, accumulator_mean, &Mx, &dMh);
-        }
-        BK_TRY(v_axpby(ctx, n, -(M / (M + dMh)), h2, 1.0, x));
-        BK_TRY(residual());
-        step += 1;
-        res->residuals[step] = r;
-    }
-    res->converged = std::isfinite(M) && res->residuals[step] < no->tol;
-    res->itnewton = step;
-    res->itlinear = itlin;
-    res->M = M;
-    double dmin = HUGE_VAL;
-    for (int i = 0; i < nroots; ++i) dmin = d[i] < dmin ? d[i] : dmin;
-    res->min_dist = nroots > 0 ? std::sqrt(dmin) : HUGE_VAL;
+    DeflNewton o;
+    BK_TRY(defl_newton(ctx, prob, x, params, nparams, roots, nroots, power, alpha, accumulator_mean, stop_plain, no->norm_inf, no->tol,
+                       no->max_iterations, lsopts, pl, res->residuals, BK_MAX_NEWTON_ITER + 1, &o));
+    res->converged = o.converged;
+    res->itnewton = o.itnewton;
+    res->itlinear = o.itlinear;
+    res->M = o.M;
+    res->min_dist = o.min_dist;
     return 0;
 }
 

@@ -1081,6 +1081,16 @@ class DeflationOperator:
                   "bk_deflation_dots")
         return [d[i] for i in range(k)], (None if e is None else [e[i] for i in range(k)])
 
+    def dist(self, u: HipVec):
+        """(d2, dinf) of bk_deflation_dist: ``sum (u - root_i)^2`` (the d of ``dots``, bit for bit) and ``max |u - root_i|``, the
+        normC(u - root) of deflated continuation's acceptance tests (src/DeflatedContinuation.jl:282, :334) from one pass."""
+        k = len(self.roots)
+        ctx = u.ctx
+        rp = (C.c_void_p * max(k, 1))(*[r.t.data_ptr() for r in self.roots])
+        d2, dinf = (C.c_double * max(k, 1))(), (C.c_double * max(k, 1))()
+        ctx.check(ctx.lib.bk_deflation_dist(ctx.h, u.n, _ptr(u.t), rp, k, d2, dinf), "bk_deflation_dist")
+        return [d2[i] for i in range(k)], [dinf[i] for i in range(k)]
+
     def combine(self, d, e=None):
         """(M, dM . du) from the sums, in the library's order: products left to right, prod_{j != i} as prefix times suffix."""
         k = len(d)

@@ -560,6 +560,50 @@ int bk_newton_deflated_exact(bk_ctx* ctx, bk_problem* prob, double* x, const dou
                              int accumulator_mean, int stop_plain, const bk_newton_opts* nopts,
                              const bk_gmres_opts* lsopts, bk_precond* pl, bk_deflated_result* res);
 
+/* ------------------------------------------------------------------ deflated continuation ---------------
+ * continuation(prob, DefCont(...), contParams) (src/DeflatedContinuation.jl:196-356; examples/SH2d-fronts.jl:168-181): the loop over
+ * steps and branches is host logic (bk_amd.deflated_continuation); these are its device parts.                                     */
+/* The normC(u - root) of the acceptance tests (:282, :334) for normC = norm and normC = norminf from ONE streaming pass per 8 roots
+ * over u and the roots (1 + 8 streams) that writes nothing: host d2[i] = sum (u - root_i)^2 and dinf[i] = max |u - root_i|.  d2[i] is
+ * the d[i] of bk_deflation_dots for the same operands bit for bit (same items per lane, same element order, same two stages).  A NaN
+ * in u - root_i makes dinf[i] NaN (norminf, src/LinearSolver.jl:4); a root equal to u gives exactly 0 in both.  Deterministic,
+ * all-reduced (sum, max).  nroots == 0 does nothing.                                                                                */
+int bk_deflation_dist(bk_ctx* ctx, size_t n, const double* u, const double* const* roots, int nroots, double* d2, double* dinf);
+/* perturb_solution of the example, x .+ amp .* rand(length(x)) (examples/SH2d-fronts.jl:181; DefCont.perturb_solution,
+ * src/DeflatedContinuation.jl:26, :272), in place with a counter-based uniform: x[i] += amp U(seed, index0 + i), where for the GLOBAL
+ * index g, in wrapping 64-bit arithmetic,
+ *   z = seed + (g + 1) 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) 0x94D049BB133111EB;
+ *   z ^= z >> 31;  U = (z >> 11) 2^-53 in [0, 1).
+ * The product and the sum are rounded one after the other (no fused multiply-add).  The result depends on (seed, g) alone -- not on
+ * the grid, the alignment or the load path -- so a rank passes index0 = slab_lo x plane size (bk_problem_nlocal) and the pieces equal
+ * the unsplit vector.  Reads and writes x once: 16 n bytes.  n == 0 does nothing.                                                   */
+int bk_vec_perturb(bk_ctx* ctx, size_t n, double* x, double amp, unsigned long long seed, unsigned long long index0);
+typedef struct {
+    int converged;               /* of the deflated Newton                                                             */
+    int itnewton;
+    int itlinear;                /* one solve per Newton step                                                          */
+    int accepted;                /* reason == 0                                                                        */
+    int reason;                  /* 0 accepted, 1 Newton not converged, 2 plain residual >= tol, 3 a known root within tol */
+    int itnewton_total;          /* entries of the residual history, itnewton + 1; the caller's buffer holds the last
+                                    min(residuals_cap, itnewton_total) of them, oldest first                           */
+    double M;                    /* M at the final x                                                                   */
+    double min_dist;             /* min_i sqrt(d_i) at the final x as the Newton saw it, +inf without roots            */
+    double plain_residual;       /* normC(F(x)) at the final x, from the Newton's last evaluation of F                 */
+    double min_dist_normC;       /* min_i normC(x - root_i) from bk_deflation_dist, +inf without roots                 */
+} bk_defcont_seek_result;
+/* _DC_get_new_solution (src/DeflatedContinuation.jl:269-286) and the duplicate test of :334 as one call: the Newton of
+ * bk_newton_deflated_exact (the same loop) from the already perturbed guess x with an open iteration count -- the seek runs
+ * max_iter_defop x newton.max_iterations iterations (:223), so the residual history goes to the caller's buffer of residuals_cap >= 1
+ * doubles -- and then, in the reference's order: the Newton converged (:274); the plain residual normC(F(x)) < tol (:281), taken from
+ * the last evaluation of F; min_i normC(x - root_i) >= tol (:282; :334 when the state sought from is among the roots, where the
+ * driver keeps it) from one pass of bk_deflation_dist.  normC is norm_inf ? norminf : norm, for the Newton and for the tests.
+ * stop_plain as in bk_newton_deflated_exact.  A root with d_i = 0 (x on a deflated state) makes M infinite: reason 1, no error.
+ * x == roots[i] (aliased) is refused with a message.  nroots == 0 is plain Newton.                                                  */
+int bk_defcont_seek(bk_ctx* ctx, bk_problem* prob, double* x, const double* params, int nparams,
+                    const double* const* roots, int nroots, double power, double alpha, int accumulator_mean,
+                    int stop_plain, int norm_inf, double tol, int max_iterations, const bk_gmres_opts* lsopts,
+                    bk_precond* pl, double* residuals, int residuals_cap, bk_defcont_seek_result* res);
+
 /* ------------------------------------------------------------------ fold points (codim 2) ---------------
  * The minimally augmented fold formulation of src/codim2/MinAugFold.jl, matrix-free (the reference assembles it for MatrixBLS /
  * MinAugMatrixBased): unknowns (x, p = params[ipar]), G(x, p) = (F(x, p), sigma(x, p)) with sigma from
