@@ -278,9 +278,12 @@ static int dense_axis_pass(bk_ctx* ctx, int n0, int n1, int n2, int axis, const 
 
 // Twiddle tables of the LDS FFT kernels (dct_fast.hip), in the slot layout of dct_core.h (twi: one padding slot per 16
 // entries): w[j] = exp(-2 pi i j / N), j < N/2 (FFT), followed by the Makhoul post-twiddles e[k] = exp(-i pi k / 2N), k <= N/2.
-std::vector<double> dct_twiddle_table(int N) {
+// Host-array form: fills tw (every slot, the padding with zeros) and returns the count of doubles; tw == nullptr only counts.
+size_t dct_twiddle_fill(int N, double* tw) {
     const int twl = dctc::tw_len(N), ewl = dctc::ew_len(N);
-    std::vector<double> tw(2 * (size_t)(twl + ewl), 0.0);
+    const size_t count = 2 * (size_t)(twl + ewl);
+    if (!tw) return count;
+    for (size_t i = 0; i < count; ++i) tw[i] = 0.0;
     for (int j = 0; j < N / 2; ++j) {
         tw[2 * (size_t)dctc::twi(j)] = std::cos(2.0 * M_PI * j / N);
         tw[2 * (size_t)dctc::twi(j) + 1] = -std::sin(2.0 * M_PI * j / N);
@@ -289,7 +292,25 @@ std::vector<double> dct_twiddle_table(int N) {
         tw[2 * (size_t)(twl + dctc::twi(k))] = std::cos(M_PI * k / (2.0 * N));
         tw[2 * (size_t)(twl + dctc::twi(k)) + 1] = -std::sin(M_PI * k / (2.0 * N));
     }
+    return count;
+}
+
+std::vector<double> dct_twiddle_table(int N) {
+    std::vector<double> tw(dct_twiddle_fill(N, nullptr));
+    dct_twiddle_fill(N, tw.data());
     return tw;
+}
+
+// Tables of the slab z-solve (dct_slab.hip) in host arrays: lam_loc[nl], the eigenvalues of the slab-local Neumann second
+// difference with az = 1 / h_z^2, and phi[2][nl], the local DCT-II basis at planes 0 and 1.
+void slab_tables_fill(int nl, double az, double* lam_loc, double* phi) {
+    for (int k = 0; k < nl; ++k) {
+        const double sn = std::sin(M_PI * k / (2.0 * nl));
+        lam_loc[k] = -4.0 * az * sn * sn;
+        const double sk = k == 0 ? std::sqrt(1.0 / nl) : std::sqrt(2.0 / nl);
+        phi[k] = sk * std::cos(M_PI * (double)k / (2.0 * nl));                 // plane 0
+        phi[nl + k] = sk * std::cos(M_PI * 3.0 * (double)k / (2.0 * nl));      // plane 1
+    }
 }
 
 int dct_plan_create(bk_ctx* ctx, int ndim, const int n[3], const double ainv[3], double shift, DctPlan** out) {
@@ -626,7 +647,13 @@ int dct_plan_create_dist(bk_ctx* ctx, const int n[3], const double ainv[3], doub
         }
         (void)hipMemcpy(p->kmap, km.data(), sizeof(unsigned) * km.size(), hipMemcpyHostToDevice);
     }
-    // slab z-solve: equal power-of-two slabs, lines divisible among the ranks, a positive shift (B_r SPD, well conditioned)
+    // slab z-solve: equal power-of-two slabs, lines divisible among the ranks, a positive shift.  shift > 0 makes every B_r SPD, not
+    // well conditioned: a line's system has the condition ((1 + 8 az)^2 + shift) / shift, and the Woodbury path loses about that many
+    // eps.  Worst error per (kx, ky) line against the exact inverse, relative to the line's max|x|, R <= 16, nl = 8 .. 512
+    // (tests/test_gpu_slab_zsolve.py on an MI355X; the float64 NumPy restatement oracle/slab_zsolve.py leaves the same figures):
+    //     shift 1:    h_z = 1: 1.4e-15     h_z = 2 pi / 32 (the benchmark's mesh): 1.3e-13     h_z = 1/16: 4.1e-11
+    //     shift 0.05: h_z = 1: 2.3e-15     h_z = 1/16: 5.6e-9;   shift 1e-3 (restatement only): up to 1e-6
+    // Lines are transformed in x-adjacent pairs by the fused kernels, so these hold relative to the larger line of a pair.
     if (slab_tables_create(ctx, p, n[2] / R, n[2] % R == 0, ainv[2]) != 0) { dct_plan_destroy(p); return -1; }
     *out = p;
     return 0;
@@ -643,13 +670,7 @@ static int slab_tables_create(bk_ctx* ctx, DctPlan* p, int nl, bool even, double
         if (even && nl >= 8 && dct_axis_fft_supported(nl) && L % R == 0 && shift > 0.0 && R - 1 <= 15) {
             const std::vector<double> tw = dct_twiddle_table(nl);
             std::vector<double> lam(nl), phi(2 * (size_t)nl);
-            for (int k = 0; k < nl; ++k) {
-                const double sn = std::sin(M_PI * k / (2.0 * nl));
-                lam[k] = -4.0 * ainv[2] * sn * sn;
-                const double sk = k == 0 ? std::sqrt(1.0 / nl) : std::sqrt(2.0 / nl);
-                phi[k] = sk * std::cos(M_PI * (double)k / (2.0 * nl));                 // plane 0
-                phi[nl + k] = sk * std::cos(M_PI * 3.0 * (double)k / (2.0 * nl));      // plane 1
-            }
+            slab_tables_fill(nl, ainv[2], lam.data(), phi.data());
             const size_t fb = 4 * L;
             if (hipMalloc(&p->twid_loc, sizeof(double) * tw.size()) != hipSuccess ||
                 hipMalloc(&p->lam_loc, sizeof(double) * nl) != hipSuccess ||

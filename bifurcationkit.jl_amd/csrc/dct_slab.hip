@@ -73,15 +73,26 @@ __global__ void __launch_bounds__(256) slab_reduced_solve(SlabK P, const double*
     const double c = 1.0 + P.lam0[ix] + P.lam1[iy];
     const double a = P.a;
     // face block of B_r^-1: A[z][z'] = sum_m phi_m(z) phi_m(z') sym_m,  C: the same with (-1)^m   (z, z' in {0, 1})
+    // Compensated (Kahan) sums: the capacitance system amplifies the rounding of A and C like its condition, and a plain running
+    // sum of nl terms made this solve 5 to 10 times less accurate than the float64 NumPy restatement (nl = 128, h = 1/16, s = 0.05:
+    // 6e-9 against 7e-10 in nu) -- compensated it is as accurate (tests/test_gpu_slab_zsolve.py).  The file is built with
+    // -ffp-contract=off and without fast-math, so the compensation survives the compiler.
     double A00 = 0, A01 = 0, A11 = 0, C00 = 0, C01 = 0, C11 = 0;
+    double eA00 = 0, eA01 = 0, eA11 = 0, eC00 = 0, eC01 = 0, eC11 = 0;
+    auto add = [](double& sum, double& comp, double x) {
+        const double y = x - comp;
+        const double t = sum + y;
+        comp = (t - sum) - y;
+        sum = t;
+    };
     for (int m = 0; m < P.nl; ++m) {
         const double t = c + P.lam_loc[m];
         const double sym = 1.0 / (t * t + P.shift);
         const double p0 = P.phi[m], p1 = P.phi[P.nl + m];
         const double q00 = p0 * p0 * sym, q01 = p0 * p1 * sym, q11 = p1 * p1 * sym;
-        A00 += q00; A01 += q01; A11 += q11;
-        if (m & 1) { C00 -= q00; C01 -= q01; C11 -= q11; }
-        else { C00 += q00; C01 += q01; C11 += q11; }
+        const double sg = (m & 1) ? -1.0 : 1.0;
+        add(A00, eA00, q00); add(A01, eA01, q01); add(A11, eA11, q11);
+        add(C00, eC00, sg * q00); add(C01, eC01, sg * q01); add(C11, eC11, sg * q11);
     }
     // P_top (rows: planes nl-2, nl-1; columns u, w) = [[a, 0], [c - a, 1]];  P_bot (rows: planes 0, 1) = [[-(c-a), -1], [-a, 0]]
     const double ca = c - a;
@@ -166,6 +177,8 @@ int slab_faces_gather(bk_ctx* ctx, const SlabK& P, const double* y, double* sbuf
     return 0;
 }
 int slab_faces_solve(bk_ctx* ctx, const SlabK& P, const double* rbuf, double* out) {
+    if (P.R < 1 || P.R - 1 > kSlabMaxFaces)                   // the kernel's register arrays hold kSlabMaxFaces block rows
+        return set_error(ctx, "slab z-solve: %d ranks, at most %d", P.R, kSlabMaxFaces + 1);
     hipLaunchKernelGGL(slab_reduced_solve, dim3((unsigned)((P.Lr + 255) / 256)), dim3(256), 0, ctx->stream, P, rbuf, out);
     BK_HIP(ctx, hipGetLastError());
     return 0;

@@ -23,7 +23,8 @@ EXCLUDED = {
     "dct_gemm": "tests/test_gpu_parity.py and tests/test_gpu_dst_transforms.py: the three dense products against each other",
     "dct_fused_dot": "tests/test_gpu_eigensolve_at_size.py: MINRES through the spectral dot of the round trip",
     "dct_slab_emulate": "tests/test_distributed.py (tests/dist_worker.py): the slab cost model",
-    "dct_slab_split": "tests/test_distributed.py (tests/dist_worker.py): the slab z-solve's half passes",
+    "dct_slab_split": "tests/test_distributed.py (tests/dist_worker.py) and tests/test_gpu_slab_zsolve.py (one process plays every "
+                      "rank): the slab z-solve's half passes",
     "dct_dist_*": "tests/test_distributed.py (tests/dist_worker.py): the distributed plan",
 }
 
