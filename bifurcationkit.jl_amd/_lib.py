@@ -243,6 +243,11 @@ SIGNATURES = {
     "bk_nf1d_predict": (I, [VP, SZ, VP, VP, VP, VP, I, c_double_p, c_double_p, c_double_p, C.POINTER(VP)]),
     "bk_normal_form_1d": (I, [VP, VP, VP, c_double_p, I, I, VP, VP, C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP, VP, VP,
                               c_double_p, c_int_p, c_int_p]),
+    "bk_cusp_dots": (I, [VP, VP, c_double_p, I, VP, VP, c_double_p]),
+    "bk_cusp_rhs": (I, [VP, VP, c_double_p, I, VP, D, VP]),
+    "bk_cusp_contract": (I, [VP, VP, c_double_p, I, VP, VP, VP, c_double_p]),
+    "bk_cusp_normal_form": (I, [VP, VP, VP, c_double_p, I, VP, VP, C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP, VP,
+                                c_double_p, c_int_p, c_int_p]),
     "bk_nfnd_dots": (I, [VP, VP, c_double_p, I, I, I, C.POINTER(VP), c_double_p]),
     "bk_nfnd_rhs": (I, [VP, VP, c_double_p, I, I, I, C.POINTER(VP), c_double_p, c_double_p, C.POINTER(VP)]),
     "bk_nfnd_contract": (I, [VP, VP, c_double_p, I, I, I, C.POINTER(VP), VP, C.POINTER(VP), c_double_p]),

@@ -10,7 +10,11 @@ path (the reference assembles the systems for MatrixBLS / MinAugMatrixBased, whi
   newton_fold_native       the same as one library call (bk_newton_fold)
   continuation_fold        continuation_fold (:369-536): PALC on G(X, p2), BorderingBLS(solver = FoldLinearSolverMinAug,
                            check_precision = false) as wired at :445-453, Secant tangent, a / b updated after every step
-                           (update!, :280-313), BT = <zeta*, zeta> and CP = tau.p recorded (test_bt_cusp, :551-576)
+                           (update!, :280-313), BT = <zeta*, zeta> and CP = tau.p recorded (test_bt_cusp, :551-576);
+                           detect_codim2 = 1 | 2: b2 = <p, B(q, q)> per point, the sign changes of CP as "cusp" points,
+                           bisected (_locate_event)
+  cusp_normal_form         cusp_normal_form (src/codim2/NormalForms.jl:15-123) call by call; cusp_normal_form_native: the same
+                           as one library call (bk_cusp_normal_form); get_normal_form on a "cusp" point of a FoldBranch
 
 Problems: SwiftHohenberg (2-D / 3-D) and SwiftHohenberg1D -- symmetric, J' = J (:79-84).  sigma_p, dpF and sigma_x are analytic
 (the Jacobians depend on the parameters only through their pointwise term), where the reference takes central differences.
@@ -20,8 +24,10 @@ preconditioned bordered solver: [J a; b' 0] for (v, sigma) and w, [J dpF; sigma_
 regular at the fold, where J \\ a and J \\ F do not converge (context option fold_bordered).
 
 Codim-2 points: on Hopf curves generalised Hopf (Bautin) points are detected, bisected and given their normal form
-(continuation_hopf(..., detect_codim2 = 1 | 2), get_normal_form on a "gh" point); Bogdanov-Takens, zero-Hopf and Hopf-Hopf points
-and the cusp on fold curves are not located (BT, CP and omega are recorded per point, and a Hopf curve stops near omega = 0).
+(continuation_hopf(..., detect_codim2 = 1 | 2), get_normal_form on a "gh" point); on fold curves cusp points, the same way
+(continuation_fold(..., detect_codim2 = 1 | 2), get_normal_form on a "cusp" point).  Bogdanov-Takens, zero-Hopf and Hopf-Hopf
+points are not located (BT and omega are recorded per point, and a Hopf curve stops near omega = 0); for the Swift-Hohenberg
+problems J' = J, so BT = <zeta*, zeta> = 1 and a fold curve has no Bogdanov-Takens point.
 
 What the two formulations have in common is written once: _MinAugProblem (the cached bordered vectors and the problem surface),
 _MinAugLinearSolver, _continuation_minaug (the PALC loop) and _newton_minaug_mirror (the Newton loop of the mirrors).
@@ -37,7 +43,7 @@ import torch
 
 from . import _lib as L
 from . import continuation as Cn
-from .hip import BorderedArray, BorderingBLS, HipVec, MatrixFreeBLS, _GMRES, _ptr, newton_opts
+from .hip import BorderedArray, BorderingBLS, HipJacobian, HipVec, MatrixFreeBLS, _GMRES, _ptr, newton_opts
 
 
 def _nanmax(*vals):
@@ -511,6 +517,8 @@ class FoldProblem(_MinAugProblem):
 
     _p1 = staticmethod(lambda X: X.p)
     _vec = staticmethod(BorderedArray)
+    keep_vw = False                                 # detection on: update keeps the bordered vectors of the point in last_vw
+    last_vw = None
 
     def _solve_terms(self, X: BorderedArray, p2: float):
         return fold_terms(self.prob, X.u, self.pvec(X.p, p2), self.ipar1, self.a, self.b, self.ls, self.bls)
@@ -529,6 +537,8 @@ class FoldProblem(_MinAugProblem):
         self.a = zs
         self.b = zs if w is v else z
         self._cache = None
+        if self.keep_vw:
+            self.last_vw = (v, w, p2)               # the null vectors of the point: b2 reuses them
         return bt
 
 
@@ -556,35 +566,126 @@ JacobianFold = _JacobianMinAug
 # ------------------------------------------------------------------------------------------ continuation_fold
 @dataclass
 class FoldBranch(_MinAugBranch):
-    """The record of continuation_fold (record_from_solution, :330-346): p1 (lens1), p2 (lens2), BT, CP per point."""
+    """The record of continuation_fold (record_from_solution, :330-346): p1 (lens1), p2 (lens2), BT, CP per point; with
+    detect_codim2 > 0 also b2 = <p, B(q, q)> per point (the quadratic coefficient of the fold, zero at a cusp) and the points
+    where CP changed sign in ``specialpoint`` (type "cusp").
+
+    A special point carries type, idx, step, p1, p2 (the point: the one after the crossing, or the located one), ``end_points``
+    = the (p1, p2) of the two states the sign change lies between, CP and CP_interval (the event there), b2, x = the state
+    BorderedArray(x, p1), a, b, bisection_steps, n_inversion, status, reach (what the point can be off by along the curve, in
+    PALC arclength: the ds of the last step that passed the sign change).  ``end_points`` is NOT a bracket of the point in p2: a
+    cusp is an extremum of p2 along the curve, so the p2 of both end states lie on the same side of it -- the point lies between
+    them along the curve (in arclength), not between their parameter values.
+
+    CP = tau.p2 changes sign at every turning point of the curve in p2.  Where b2 vanishes with it the point is a cusp; where
+    b2 != 0 it is <p, dF/dp1> that vanishes instead (the fold curve turns without the fold degenerating).  The reference labels
+    both :cusp (codim2.jl:559-570); so does this record, and b2 tells them apart."""
     BT: list = field(default_factory=list)
     CP: list = field(default_factory=list)
+    b2: list = field(default_factory=list)
+    specialpoint: list = field(default_factory=list)
+    lens2: str | None = None
 
 
 def _norminf_fold(z):
     return _nanmax(z.u.norminf(), abs(z.p))
 
 
+def cusp_dots(prob, x: HipVec, pars, v: HipVec, w: HipVec):
+    """One pass that writes nothing (bk_cusp_dots): (<w, d2F(x)[v, v]>, <v, v>, <w, w>, <v, w>)."""
+    ctx = prob.ctx
+    out = (C.c_double * 4)()
+    ctx.check(ctx.lib.bk_cusp_dots(prob.h, _ptr(x.t), _carr(pars), len(pars), _ptr(v.t), _ptr(w.t), out), "bk_cusp_dots")
+    return out[0], out[1], out[2], out[3]
+
+
+def cusp_b2(prob, x: HipVec, pars, v: HipVec, w: HipVec) -> float:
+    """b2 = <p, B(q, q)> with q = v / |v|, p = w / <q, w> from the unnormalised bordered vectors v, w of a fold-curve point:
+    <w, B(v, v)> / (|v| <v, w>), one cusp_dots pass and no vector written."""
+    d = cusp_dots(prob, x, pars, v, w)
+    return d[0] / (math.sqrt(d[1]) * d[3])
+
+
 def continuation_fold(prob, fold_guess: BorderedArray, p2: float, lens2: str, a: HipVec, b: HipVec, ls: _GMRES,
                       cp: Cn.ContinuationPar, theta=0.5, norm_inf=True, update_minaug_every_step=1, save_sol=False,
-                      ds_sequence=None, verbosity=0, bls: BorderingBLS | MatrixFreeBLS | None = None) -> FoldBranch:
+                      ds_sequence=None, verbosity=0, bls: BorderingBLS | MatrixFreeBLS | None = None,
+                      detect_codim2=0) -> FoldBranch:
     """continuation_fold(prob, alg = PALC(tangent = Secant()), foldpointguess, par, lens1, lens2, a, b, options_cont) (:369-453):
     PALC on G(X, p2) through continuation.newton_palc with BorderingBLS(solver = FoldLinearSolverMinAug(), check_precision =
     false) (:445-453), Secant tangent only (the reference warns against Bordered on folds, :390-392), the two starting points of
     continuation (Continuation.jl:349-456) by newton on G, step-size control of continuation.py.  After every converged step a, b
     are updated (update_minaug_every_step = 1) and BT, CP recorded.  ``ds_sequence`` (optional) replaces the step-size control by
-    a fixed list of steps (comparisons with a restatement).  Codim-2 points are not located.
+    a fixed list of steps (comparisons with a restatement).
     ``bls`` (optional): the bordered solver of the formulation's OWN solves -- MatrixFreeBLS(ls, use_pl=True) runs the bordered
     vectors and the fold linear solver on the preconditioned bordered system; the outer PALC solve stays BorderingBLS over the fold
-    linear solver, as in the reference (:449)."""
-    br = FoldBranch()
+    linear solver, as in the reference (:449).
+
+    ``detect_codim2`` (the test_bt_cusp event, :432, :551-576, with the semantics of continuation_hopf): 0 locates nothing and
+    issues exactly the library calls of the plain curve.  1: after every converged step b2 of the new point is recorded from the
+    bordered vectors the step solved (cusp_b2: one reducing pass), and every sign change of CP between consecutive points goes
+    to br.specialpoint as type "cusp" with status "guess".  2: each sign change is bisected along the curve (_locate_event; the
+    event is the p2 component of the orientation-keeping secant tangent) and the special point keeps the located state; the
+    curve continues from the state it had before the bisection, so the recorded points are those of detect_codim2 = 1.  The
+    secant of a point spans the step that led to it, so a sign change of CP between the points i - 1 and i places the extremum
+    of p2 between the points i - 2 and i: the bisection is handed that bracket and the sum of the two steps (the loop itself is
+    the one the Hopf curve uses); as the bisection states close in, their secant becomes the local tangent.  See
+    FoldBranch for the fields of a special point, for why its ``end_points`` are no bracket in p2, and for the sign changes of CP
+    with b2 != 0.  Bogdanov-Takens and zero-Hopf points are not located."""
+    br = FoldBranch(lens2=lens2)
+    P = FoldProblem(prob, lens2, a, b, ls, bls)
+    P.keep_vw = bool(detect_codim2)
+    if detect_codim2 and update_minaug_every_step != 1:
+        raise ValueError("detect_codim2 needs the bordered vectors of every point (update_minaug_every_step = 1)")
+    normC = _norminf_fold if norm_inf else (lambda z: z.norm())
+
+    def b2_at(X, vw):
+        v, w, p2_ = vw
+        return cusp_b2(prob, X.u, P.pvec(X.p, p2_), v, w)
 
     def record_x(X, bt, tau):
         br.p1.append(X.p); br.BT.append(bt); br.CP.append(tau.p)
+        if detect_codim2:
+            with _solver_state_kept(prob.ctx):
+                br.b2.append(b2_at(X, P.last_vw))
 
-    _continuation_minaug(FoldProblem(prob, lens2, a, b, ls, bls), FoldLinearSolverMinAug(), "fold", br, fold_guess, p2, cp, theta,
-                         _norminf_fold if norm_inf else (lambda z: z.norm()), update_minaug_every_step, save_sol, ds_sequence,
-                         verbosity, record_x, skipped=lambda X: float("nan"), describe=lambda X: f"p1={X.p:+.8f}")
+    def coords(s):
+        return (float(s.u.p), float(s.p))
+
+    before = []                                     # (z_old, ds) of the previous step: the state two points back
+
+    def after_record(z, z_old, tau, ds_taken, nopt, bls_):
+        # record() has appended the point: CP[-1] belongs to z, CP[-2] to z_old.  CP of a point is the secant over the step that
+        # led to it, so a sign change between the points i - 1 and i puts the extremum of p2 between the points i - 2 and i:
+        # the bisection starts from that bracket, with the two steps that span it
+        z_far, ds_far = before.pop() if before else (z_old, 0.0)
+        if detect_codim2 > 1:
+            before.append((z_old.copy(), ds_taken))
+        if len(br.CP) < 2 or not _sign_change(br.CP[-2], br.CP[-1]):
+            return
+        i = len(br.CP) - 1
+        sp = dict(type="cusp", idx=i, step=i, p1=float(z.u.p), p2=float(z.p), end_points=(coords(z_old), coords(z)),
+                  CP=br.CP[-1], CP_interval=(br.CP[-2], br.CP[-1]), b2=br.b2[-1], x=z.u.copy(), a=P.a, b=P.b, bisection_steps=0,
+                  n_inversion=0, status="guess", reach=abs(ds_taken))
+        if detect_codim2 > 1:
+            b2 = [br.b2[-1]]
+
+            def event(zc, tau_b, previous):
+                # the corrector's last residual left the bordered vectors of zc in the cache: b2 costs one reducing pass
+                v, w, _ = P.terms(zc.u, zc.p)
+                b2[0] = b2_at(zc.u, (v, w, zc.p))
+                return float(tau_b.p)
+
+            with _solver_state_kept(prob.ctx):
+                r = _locate_event(P, z, z_far, tau, ds_taken + ds_far, br.CP[-1], event, coords, cp, theta, nopt, bls_, normC)
+            zc, vals = r["z"], [br.CP[-2] if v != v else v for v in r["values"]]
+            sp.update(p1=float(zc.u.p), p2=float(zc.p), end_points=tuple(r["ends"]), CP=r["value"], CP_interval=tuple(vals),
+                      b2=b2[0], x=zc.u.copy(), bisection_steps=r["bisection_steps"], n_inversion=r["n_inversion"],
+                      status=r["status"], reach=r["reach"])
+        br.specialpoint.append(sp)
+
+    _continuation_minaug(P, FoldLinearSolverMinAug(), "fold", br, fold_guess, p2, cp, theta, normC, update_minaug_every_step,
+                         save_sol, ds_sequence, verbosity, record_x, skipped=lambda X: float("nan"),
+                         describe=lambda X: f"p1={X.p:+.8f}", after_record=after_record if detect_codim2 else None)
     return br
 
 
@@ -1026,21 +1127,29 @@ def _first_lyapunov(P: HopfProblem, X: HopfVec, vw=None) -> complex:
         return complex(hopf_normal_form_native(P.prob, X, zeta, zeta_star, P.ls).nf.b)
 
 
-def _locate_gh(P: HopfProblem, z, z_old, tau, ds, gh_after: float, cp, theta, nopt, bls, normC) -> dict:
-    """locate_event! (src/events/EventDetection.jl:28-175) for the sign change of GH between z_old and z, on copies of the state:
-    ds, the step that led from z_old to z, is reversed and halved (the first point is the middle of the crossing step), then PALC
-    corrector steps are taken with the step-size control off, ds halved after every step and its sign flipped whenever GH changed sign, until cp.max_bisection_steps, cp.n_inversion, |ds| < cp.dsmin_bisection or an
-    unconverged corrector.  The tangent keeps the orientation of the curve (Secant with the sign of the ds of the step), a and b
-    stay those of the point after the crossing, and the problem's a, b, cache and GMRES count are restored on exit.  Returns the
-    fields of the special point: the last state, its p2 and GH, the bracket, the steps taken and why the bisection ended."""
-    keep = (P.a, P.b, P._cache, P.itlinear, P.last_vw)
+def _locate_event(P: _MinAugProblem, z, z_old, tau, ds, ev_after: float, event, coords, cp, theta, nopt, bls, normC) -> dict:
+    """locate_event! (src/events/EventDetection.jl:28-175) for the sign change of an event between z_old and z, on copies of the
+    state: ds, the step that led from z_old to z, is reversed and halved (the first point is the middle of the crossing step), then
+    PALC corrector steps are taken with the step-size control off, ds halved after every step and its sign flipped whenever the
+    event changed sign, until cp.max_bisection_steps, cp.n_inversion, |ds| < cp.dsmin_bisection or an unconverged corrector.  The
+    tangent keeps the orientation of the curve (Secant with the sign of the ds of the step), a and b stay those of the point after
+    the crossing, and the problem's a, b, cache, GMRES count and kept bordered vectors are restored on exit.
+    ``event(zc, tau_b, previous)`` -> the event value at the new state zc with its tangent tau_b; ``coords(z)`` -> what is kept of
+    the two end states.  Returns dict(z = the last state, value = its event value, ends = [coords of the state before the
+    crossing, coords of the state after it] as the bisection moved them, values = the event values there, bisection_steps,
+    n_inversion, status = why the bisection ended, reach = |ds| of the last step that passed the crossing -- the first, halved,
+    step when none did: the halved steps after it add up to no more than this, so it is what the last state can still be off by
+    along the curve)."""
+    keep = (P.a, P.b, P._cache, P.itlinear, getattr(P, "last_vw", None))
     zc, zp_ = z.copy(), z_old.copy()
     tau_b = tau.copy()
-    interval = [float(z_old.p), float(z.p)]
-    ind = 1                                          # the end of the bracket the current state replaces
-    sign = gh_after > 0
+    ends = [coords(z_old), coords(z)]
+    values = [math.nan, ev_after]
+    ind = 1                                          # the end the current state replaces
+    sign = ev_after > 0
     ds_b = -ds / 2.0
-    gh, steps, n_inv, status = gh_after, 0, 0, "max_bisection_steps"
+    ev, steps, n_inv, status = ev_after, 0, 0, "max_bisection_steps"
+    reach = abs(ds_b)
     try:
         while steps < cp.max_bisection_steps:
             if n_inv >= cp.n_inversion:
@@ -1057,21 +1166,35 @@ def _locate_gh(P: HopfProblem, z, z_old, tau, ds, gh_after: float, cp, theta, no
             zc.copyto_(sol.u)
             steps += 1
             tau_b = Cn.secant_tangent(zc, zp_, ds_b, theta)
-            v, w, _ = P.terms(zc.u, zc.p)
-            gh = _gh_value(_first_lyapunov(P, zc.u, (v, w, zc.p)), gh)
-            if (gh > 0) == sign:
+            ev = event(zc, tau_b, ev)
+            if (ev > 0) == sign:
                 ds_b /= 2.0
             else:
+                reach = abs(ds_b)
                 ds_b /= -2.0
                 n_inv += 1
                 ind = 1 - ind
-                sign = gh > 0
-            interval[ind] = float(zc.p)
+                sign = ev > 0
+            ends[ind] = coords(zc)
+            values[ind] = ev
     finally:
         P.a, P.b, P._cache, P.itlinear = keep[:4]
-        P.last_vw = keep[4]
-    return dict(x=zc.u.copy(), p2=float(zc.p), GH=gh, interval=tuple(sorted(interval)), bisection_steps=steps, n_inversion=n_inv,
-                status=status)
+        if hasattr(P, "last_vw"):
+            P.last_vw = keep[4]
+    return dict(z=zc, value=ev, ends=ends, values=values, bisection_steps=steps, n_inversion=n_inv, status=status, reach=reach)
+
+
+def _locate_gh(P: HopfProblem, z, z_old, tau, ds, gh_after: float, cp, theta, nopt, bls, normC) -> dict:
+    """_locate_event for the sign change of GH between z_old and z: the event is the first Lyapunov coefficient from the bordered
+    vectors of the new state.  Returns the fields of the special point: the last state, its p2 and GH, the bracket, the steps
+    taken and why the bisection ended."""
+    def event(zc, tau_b, previous):
+        v, w, _ = P.terms(zc.u, zc.p)
+        return _gh_value(_first_lyapunov(P, zc.u, (v, w, zc.p)), previous)
+
+    r = _locate_event(P, z, z_old, tau, ds, gh_after, event, lambda s: float(s.p), cp, theta, nopt, bls, normC)
+    return dict(x=r["z"].u.copy(), p2=float(r["z"].p), GH=r["value"], interval=tuple(sorted(r["ends"])),
+                bisection_steps=r["bisection_steps"], n_inversion=r["n_inversion"], status=r["status"])
 
 
 # ================================================================================================== Hopf normal form
@@ -1366,6 +1489,117 @@ def _bautin_from_branch(br, ind: int, prob, ls: _GMRES, tol, max_iterations, nor
         return bautin_normal_form_native(prob, hp, ls, lens2=br.lens2, bls=bls)
 
 
+# ------------------------------------------------------------------------------------------ cusp normal form
+# cusp_normal_form (src/codim2/NormalForms.jl:15-123; Kuznetsov 1999) for the Swift-Hohenberg problems, matrix-free, at a fold
+# (x, params) with q = zeta, p = zeta*, |q| = 1, <q, p> = 1 (J' = J: p may be q itself):
+#
+#   b2 = <p, B(q, q)>,   [J q; p' 0][H2; s] = [b2 q - B(q, q); 0]   (:107-109),   c = (<p, C(q, q, q)> + 3 <p, B(q, H2)>) / 6   (:112-113)
+#
+#   cusp_dots, cusp_rhs, cusp_contract   the device passes (bk_cusp_dots, bk_cusp_rhs, bk_cusp_contract)
+#   cusp_normal_form                     the computation call by call on the plugin surface (d2F, bk_d3f, inner products, bls)
+#   cusp_normal_form_native              the same as one library call (bk_cusp_normal_form)
+@dataclass
+class CuspNormalForm:
+    """The reference's nf = (c = c,) plus the vector of the computation."""
+    c: float | None = None
+
+
+@dataclass
+class Cusp:
+    """The reference's Cusp record (x0, params, lens = (lens1, lens2), zeta, zeta_star, nf = (c,)) plus b2 = <zeta*, B(zeta, zeta)>
+    (zero at a cusp; not small: the point is a turning point of the fold curve in lens2 that is no cusp, see FoldBranch), H2 and
+    what the one bordered solve reported: ``converged``, ``itlinear`` and, from the native call, ``unconverged_solves``."""
+    x0: object
+    params: list
+    lens: tuple
+    zeta: object
+    zeta_star: object
+    nf: CuspNormalForm = field(default_factory=CuspNormalForm)
+    b2: float | None = None
+    H2: object = None
+    converged: bool | None = None
+    itlinear: tuple = ()
+    unconverged_solves: int | None = None
+
+
+def cusp_rhs(prob, x: HipVec, pars, q: HipVec, b2: float) -> HipVec:
+    """One pass over (x, q) (bk_cusp_rhs): b2 q - d2F(x)[q, q], the right-hand side of the H2 solve."""
+    return _into_similar(prob, "bk_cusp_rhs", x, pars, _ptr(q.t), float(b2))
+
+
+def cusp_contract(prob, x: HipVec, pars, q: HipVec, p: HipVec, H2: HipVec):
+    """One pass over (x, q, p, H2) (bk_cusp_contract): (<p, d3F(x)[q, q, q]>, <p, d2F(x)[q, H2]>)."""
+    ctx = prob.ctx
+    out = (C.c_double * 2)()
+    ctx.check(ctx.lib.bk_cusp_contract(prob.h, _ptr(x.t), _carr(pars), len(pars), _ptr(q.t), _ptr(p.t), _ptr(H2.t), out),
+              "bk_cusp_contract")
+    return out[0], out[1]
+
+
+def _cusp_lens(prob, lens2):
+    return (prob.lens, lens2)
+
+
+def cusp_normal_form(prob, x: HipVec, pars, q: HipVec, p: HipVec, ls: _GMRES, bls: BorderingBLS | MatrixFreeBLS | None = None,
+                     lens2=None) -> Cusp:
+    """cusp_normal_form (:100-123) call by call on the plugin surface at the fold (x, pars) with q, p normalised (|q| = 1,
+    <q, p> = 1; they may be the same vector): h2 = d2F(q, q), b2 = <p, h2>, H2 = bls(J, q, p, 0, b2 q - h2, 0) and
+    c = (<p, d3F(q, q, q)> + 3 <p, d2F(q, H2)>) / 6, every tensor materialised and every inner product its own pass.
+    ``bls``: BorderingBLS (default, check_precision = false), MatrixFreeBLS(ls) or MatrixFreeBLS(ls, use_pl=True)."""
+    from .normal_form1d import d3F
+    bls = bls if bls is not None else BorderingBLS(ls, check_precision=False)
+    pars = [float(v) for v in pars]
+    nrm = q.inner(p)
+    if not abs(nrm - 1) <= 1e-8:
+        raise ValueError(f"Error of precision in normalization: <q, p> = {nrm}, expected 1")
+    h2 = d2F(prob, x, pars, q, q)
+    b2 = p.inner(h2)
+    rhs = q.copy().scale_(b2).add_(h2, -1.0)
+    J = HipJacobian(prob, x, pars)
+    H2, _, cv, it = bls(J, q, p, 0.0, rhs, 0.0)
+    c = (p.inner(d3F(prob, x, pars, q, q, q)) + 3.0 * p.inner(d2F(prob, x, pars, q, H2))) / 6.0
+    it = tuple(int(i) for i in np.atleast_1d(it))
+    return Cusp(x0=x, params=pars, lens=_cusp_lens(prob, lens2), zeta=q, zeta_star=p, nf=CuspNormalForm(c), b2=b2, H2=H2,
+                converged=bool(cv), itlinear=it)
+
+
+def cusp_normal_form_native(prob, x: HipVec, pars, q: HipVec, p: HipVec, ls: _GMRES,
+                            bls: BorderingBLS | MatrixFreeBLS | None = None, lens2=None) -> Cusp:
+    """The same as one library call (bk_cusp_normal_form); with ``bls = MatrixFreeBLS(ls, use_pl=True)`` under the context option
+    fold_bordered = 1, set and put back around the call."""
+    bls = bls if bls is not None else BorderingBLS(ls, check_precision=False)
+    ctx = prob.ctx
+    pars = [float(v) for v in pars]
+    H2 = x.similar()
+    coef = (C.c_double * 2)()
+    cv = C.c_int()
+    it = (C.c_int * 2)()
+    bordered = isinstance(bls, MatrixFreeBLS) and bls.use_pl
+    bo, lo = _bls_opts(bls), ls._opts()
+    bad0 = ctx.get_option("cusp_unconverged_solves")
+    with _fold_bordered(ctx, bordered):
+        ctx.check(ctx.lib.bk_cusp_normal_form(ctx.h, prob.h, _ptr(x.t), _carr(pars), len(pars), _ptr(q.t), _ptr(p.t), C.byref(bo),
+                                              C.byref(lo), ls._pl(), _ptr(H2.t), coef, C.byref(cv), it), "bk_cusp_normal_form")
+    return Cusp(x0=x, params=pars, lens=_cusp_lens(prob, lens2), zeta=q, zeta_star=p, nf=CuspNormalForm(coef[1]), b2=coef[0], H2=H2,
+                converged=bool(cv.value), itlinear=(it[0], it[1]) if not isinstance(bls, MatrixFreeBLS) else (it[0],),
+                unconverged_solves=int(ctx.get_option("cusp_unconverged_solves") - bad0))
+
+
+def _cusp_from_branch(br, ind: int, prob, ls: _GMRES, tol, max_iterations, norm_inf, bls=None) -> Cusp:
+    """A "cusp" point of a FoldBranch: newton_fold_native in lens1 at the located p2 from the located state -> q = v / |v|,
+    p = w / <q, w> -> cusp_normal_form_native (the normal form at the REFINED fold point of the located p2)."""
+    sp = br.specialpoint[ind]
+    X = sp["x"]
+    with _lens2_at(prob, br.lens2, sp["p2"]):
+        s = newton_fold_native(prob, X.u, X.p, sp["a"], sp["b"], ls, bls, tol=tol, max_iterations=max_iterations,
+                               norm_inf=norm_inf)
+        if not s["converged"]:
+            raise RuntimeError(f"get_normal_form: newton_fold did not converge from the located point (residuals {s['residuals']})")
+        q = s["v"].copy().scale_(1.0 / s["v"].norm())
+        p = s["w"].copy().scale_(1.0 / q.inner(s["w"]))
+        return cusp_normal_form_native(prob, s["u"].u, prob._pvec(s["u"].p), q, p, ls, bls, lens2=br.lens2)
+
+
 def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, max_iterations=15, norm_inf=False, seed=0,
                     bls=None, refine=True):
     """get_normal_form(br, ind) (src/NormalForms.jl:1102-1204) for a point of type "hopf" of a branch of
@@ -1376,12 +1610,17 @@ def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, 
     "nd" points, and "bp" / "fold" points of any other problem, have no normal form here.  A point of type "gh" of a HopfBranch
     (continuation_hopf(..., detect_codim2 > 0)) returns its Bautin record: newton_hopf_native at the located p2 ->
     hopf_eigenpair -> hopf_normal_form_native -> bautin_normal_form_native.  For "hopf" and "gh" points ``bls`` is the bordered
-    solver of newton_hopf_native and bautin_normal_form_native (MatrixFreeBLS(ls, use_pl=True): option hopf_bordered)."""
+    solver of newton_hopf_native and bautin_normal_form_native (MatrixFreeBLS(ls, use_pl=True): option hopf_bordered).  A point of
+    type "cusp" of a FoldBranch (continuation_fold(..., detect_codim2 > 0)) returns its Cusp record: newton_fold_native in lens1 at
+    the located p2 -> q = v / |v|, p = w / <q, w> -> cusp_normal_form_native, ``bls`` the bordered solver of both
+    (MatrixFreeBLS(ls, use_pl=True): option fold_bordered)."""
     from . import normal_form1d as N1
     sh = N1.is_sh_problem(prob)                     # decided before the branch is looked at
     kind = br.specialpoint[ind].get("type")
     if kind == "gh" and isinstance(br, HopfBranch):
         return _bautin_from_branch(br, ind, prob, ls, tol, max_iterations, norm_inf, bls)
+    if kind == "cusp" and isinstance(br, FoldBranch):
+        return _cusp_from_branch(br, ind, prob, ls, tol, max_iterations, norm_inf, bls)
     if sh and kind in ("bp", "fold"):
         return N1.get_normal_form1d(br, ind, prob, ls, bls=bls, eig=eig, nev=nev, refine=refine, tol=tol,
                                     max_iterations=max_iterations, norm_inf=norm_inf)

@@ -104,6 +104,7 @@ struct bk_ctx {
         double hopf_nf_unconverged = 0.0;                                          // bk_hopf_normal_form: solves (of three per call) that returned unconverged
         double bautin_unconverged = 0.0;                                           // bk_bautin_normal_form: solves (of four per call) that returned unconverged
         double nf1d_unconverged = 0.0;                                             // bk_normal_form_1d: solves (three with bordering, two matrix-free) that returned unconverged
+        double cusp_unconverged = 0.0;                                             // bk_cusp_normal_form: calls whose one bordered solve returned unconverged
         double nfnd_unconverged = 0.0;                                             // bk_normal_form_nd: solves (of 1 + N (N + 1) / 2 per call) that returned unconverged
     } diag;
     double* diag_slot(const std::string& key) {
@@ -118,6 +119,7 @@ struct bk_ctx {
         if (key == "hopf_nf_unconverged_solves") return &diag.hopf_nf_unconverged;
         if (key == "bautin_unconverged_solves") return &diag.bautin_unconverged;
         if (key == "nf1d_unconverged_solves") return &diag.nf1d_unconverged;
+        if (key == "cusp_unconverged_solves") return &diag.cusp_unconverged;
         if (key == "nfnd_unconverged_solves") return &diag.nfnd_unconverged;
         return nullptr;
     }

@@ -851,6 +851,36 @@ int bk_normal_form_1d(bk_ctx* ctx, bk_problem* prob, const double* x, const doub
                       const double* zeta, const double* zeta_star, const bk_bordering_opts* bopts, const bk_gmres_opts* lsopts,
                       bk_precond* pl, double* psi01, double* psi20, double coef[5], int* converged, int itlinear[3]);
 
+/* ------------------------------------------------------------------ cusp points on fold curves -------------
+ * The cusp test value along continuation_fold and cusp_normal_form (src/codim2/NormalForms.jl:15-123; Kuznetsov 1999), matrix-free,
+ * for BK_PDE_SH (2-D / 3-D) and BK_PDE_SH1D (any other problem: the error of the fold entries above).  At a fold (x, params) with
+ * q = zeta spanning ker J, p = zeta* spanning ker J' = J, |q| = 1 and <q, p> = 1 (the two pointers may be equal), B = d2F and
+ * C = d3F pointwise and analytic:
+ *   b2 = <p, B(q, q)>,   [J q; p' 0][H2; s] = [b2 q - B(q, q); 0]  (:107-109),   c = (<p, C(q, q, q)> + 3 <p, B(q, H2)>) / 6  (:112-113).
+ * b2 vanishes at a cusp; c is the coefficient of the cusp normal form.                                                       */
+/* One streaming pass over u, v, w that writes nothing: host out[4] = (<w, d2F(u)[v, v]>, <v, v>, <w, w>, <v, w>).  For the
+ * unnormalised bordered vectors v, w of a fold-curve point b2 = out[0] / (sqrt(out[1]) out[3]) (q = v / |v|, p = w / <q, w>).
+ * Deterministic, all-reduced.                                                                                               */
+int bk_cusp_dots(bk_problem* prob, const double* u, const double* params, int nparams, const double* v, const double* w,
+                 double out[4]);
+/* One pass over u and q: out = b2 q - d2F(u)[q, q], the right-hand side of the H2 solve (:107-108).  out aliases no input.   */
+int bk_cusp_rhs(bk_problem* prob, const double* u, const double* params, int nparams, const double* q, double b2, double* out);
+/* One streaming pass over u, q, p, H2 (32 N bytes): host out[2] = (<p, d3F(u)[q, q, q]>, <p, d2F(u)[q, H2]>);
+ * c = (out[0] + 3 out[1]) / 6 (:112-113).  Deterministic, all-reduced.                                                       */
+int bk_cusp_contract(bk_problem* prob, const double* u, const double* params, int nparams, const double* q, const double* p,
+                     const double* H2, double out[2]);
+/* The whole of cusp_normal_form's computation at (x, params): the pass of bk_cusp_dots on (x, q, p), the pass of bk_cusp_rhs,
+ * ONE bordered solve bls(J, q, p, 0, rhs, 0) (:109) and the pass of bk_cusp_contract.  bopts->kind == 0: BorderingBLS as
+ * bk_bls_bordering (two GMRES solves, J \ rhs and J \ q; check_precision / k / tol as there); kind == 1: as bk_bls_matrixfree;
+ * context option "fold_bordered" = 1 (read once per call; bopts->kind is then not read): as bk_bls_matrixfree_pl, pl must be
+ * given.  q and p come normalised; unless |<q, p> - 1| <= 1e-8 the call is an error.  coef[2] = (b2, c); H2 is an output and
+ * aliases no input.  itlinear[2] = the GMRES counts (one solve: the second is 0).  J alone is singular at the point, so an
+ * unconverged solve is no error (the reference logs it, :110): *converged = 0 and the context counter
+ * "cusp_unconverged_solves" grows by 1.                                                                                     */
+int bk_cusp_normal_form(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, const double* q,
+                        const double* p, const bk_bordering_opts* bopts, const bk_gmres_opts* lsopts, bk_precond* pl, double* H2,
+                        double coef[2], int* converged, int itlinear[2]);
+
 /* ------------------------------------------------------------------ normal form, 2-d and 3-d kernels -------------
  * get_normal_formNd (src/NormalForms.jl:648-896), matrix-free, for BK_PDE_SH (2-D / 3-D) and BK_PDE_SH1D (any other problem:
  * the error of the fold entries above) at a branch point (x, params) whose kernel has dimension N = 2 or 3.  J' = J, the
