@@ -99,6 +99,10 @@ class BisectionResult(C.Structure):
                 ("vals_re", C.c_double * (BK_MAX_NEV + 1)), ("vals_im", C.c_double * (BK_MAX_NEV + 1))]
 
 
+class SolveResult(C.Structure):
+    _fields_ = [("converged", C.c_int), ("niter", C.c_int), ("resnorm", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_double_p, C.c_int, C.c_int)
 SENDRECV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, c_double_p, C.c_size_t, C.c_int, c_double_p, C.c_size_t, C.c_int)
 
@@ -253,6 +257,19 @@ SIGNATURES = {
     "bk_nfnd_contract": (I, [VP, VP, c_double_p, I, I, I, C.POINTER(VP), VP, C.POINTER(VP), c_double_p]),
     "bk_normal_form_nd": (I, [VP, VP, VP, c_double_p, I, I, I, C.POINTER(VP), C.POINTER(GmresOpts), VP, VP, C.POINTER(VP),
                               c_double_p, c_int_p, c_int_p]),
+    "bk_potrap_create": (I, [VP, I, C.POINTER(VP)]),
+    "bk_potrap_destroy": (I, [VP]),
+    "bk_potrap_set_section": (I, [VP, VP, VP]),
+    "bk_potrap_residual": (I, [VP, VP, D, c_double_p, I, VP, c_double_p]),
+    "bk_potrap_jvp": (I, [VP, VP, D, c_double_p, I, VP, D, VP, c_double_p]),
+    "bk_potrap_op_create": (I, [VP, VP, D, c_double_p, I, C.POINTER(VP)]),
+    "bk_potrap_update_section": (I, [VP, VP, D, c_double_p, I]),
+    "bk_potrap_dparam": (I, [VP, VP, D, c_double_p, I, I, VP]),
+    "bk_precond_potrap_create": (I, [VP, D, D, C.POINTER(VP)]),
+    "bk_precond_potrap_set_period": (I, [VP, D]),
+    "bk_precond_potrap_transform_paths": (I, [VP, c_int_p]),
+    "bk_potrap_get_section": (I, [VP, VP, VP]),
+    "bk_potrap_solve": (I, [VP, VP, VP, VP, D, VP, c_double_p, C.POINTER(GmresOpts), C.POINTER(SolveResult)]),
 }
 
 _lib = None

@@ -46,6 +46,7 @@ struct DctPlan {
                                               // 2: DST-I, 2x2 block symbol of the two cGL fields (blk_a, blk_b)
     double blk_a = 0.0, blk_b = 0.0;
     int batch = 1;                            // stacked fields sharing the transform (cGL: 2)
+    int last_path[2] = {-1, -1};              // dst_transform: what dense_axis_pass dispatched to per axis (dst_plan_last_path)
     // hand-written fp64-MFMA path of the sine transforms (dense_mfma.hip): per axis the half-size blocks Te, To, their
     // transposes, and the eigenvalues in the permuted spectral order [even k | odd k]
     double* mf[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
@@ -235,12 +236,18 @@ int dense_gemm_axis_pass(bk_ctx* ctx, int n0, int n1, int n2, int axis, const do
                          double* out);
 // MT = M' (row-major).  Option dct_gemm: 1 (default) the hand-written fp64-MFMA product (dense_mfma.hip), 2 rocBLAS dgemm
 // (the cross-check; rounds 1-2 ran on it), 0 the one-thread-per-output kernel.
+// *path (optional) receives the kernel this call dispatched to: 1 the matrix-core product, 0 the one-thread-per-output kernel,
+// 2 rocBLAS.
 static int dense_axis_pass(bk_ctx* ctx, int n0, int n1, int n2, int axis, const double* M, const double* MT, const double* in,
-                           double* out) {
+                           double* out, int* path = nullptr) {
     const int N = axis == 0 ? n0 : (axis == 1 ? n1 : n2);
     const size_t total = (size_t)n0 * n1 * n2;
     const int gemm = (int)ctx->opt("dct_gemm", 1.0);
-    if (N >= 32 && gemm == 1) return dense_gemm_axis_pass(ctx, n0, n1, n2, axis, M, MT, in, out);
+    if (N >= 32 && gemm == 1) {
+        if (path) *path = 1;
+        return dense_gemm_axis_pass(ctx, n0, n1, n2, axis, M, MT, in, out);
+    }
+    if (path) *path = (N < 32 || gemm == 0) ? 0 : 2;
     if (N < 32 || gemm == 0) {
         hipLaunchKernelGGL(dct_axis_direct, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, n0, n1, n2, axis,
                            M, in, out);
@@ -456,6 +463,26 @@ static int dst_apply(bk_ctx* ctx, DctPlan* p, const double* v, double* out) {
     BK_TRY(pass(0, p->t1, out));
     return 0;
 }
+
+// The transform alone, for callers with a symbol of their own between the two halves (potrap.hip: the time solve of the
+// space-time preconditioner): the DST-I along both axes of every stacked field of a dst_plan_create plan, in -> out through the
+// plan's scratch (out may alias in).  The sine matrix is symmetric and its own inverse; `inverse` only picks the axis order of
+// dst_apply's second half.  The spectrum is in natural mode order, the one of dst_plan_lam.  These are the dense passes of
+// dst_apply: the matrix-core product from 32 points per axis on, one thread per output below (dense_axis_pass).
+int dst_transform(bk_ctx* ctx, DctPlan* p, int inverse, const double* in, double* out) {
+    if (!p || p->kind < 1) return set_error(ctx, "dst_transform: not a sine-transform plan");
+    const int n0 = p->n[0], n1 = p->n[1], nb = p->batch;
+    auto pass = [&](int a, const double* i, double* o) -> int {
+        ProfScope ps(ctx, "dct_pass", 16.0 * p->total);
+        return dense_axis_pass(ctx, n0, n1, nb, a, p->T[a], p->T[a], i, o, &p->last_path[a]);
+    };
+    BK_TRY(pass(inverse ? 1 : 0, in, p->t1));
+    return pass(inverse ? 0 : 1, p->t1, out);
+}
+const double* dst_plan_lam(const DctPlan* p, int axis) { return p->lam[axis]; }
+double* dst_plan_scratch(const DctPlan* p) { return p->t2; }
+// the kernel dst_transform's last pass along `axis` dispatched to, as dense_axis_pass reported it (-1: none yet)
+int dst_plan_last_path(const DctPlan* p, int axis) { return p->last_path[axis]; }
 
 void dct_plan_destroy(DctPlan* p) {
     if (!p) return;

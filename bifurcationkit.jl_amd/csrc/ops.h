@@ -69,6 +69,12 @@ int dct_plan_create(bk_ctx* ctx, int ndim, const int n[3], const double ainv[3],
 // distributed (z-slab) variant: n = GLOBAL extents; this rank owns planes [zlo, zhi)
 int dct_plan_create_dist(bk_ctx* ctx, const int n[3], const double ainv[3], double shift, int zlo, int zhi, DctPlan** out);
 void dct_plan_destroy(DctPlan* p);
+// DST-I plan of the Dirichlet 5-point Laplacian for `batch` stacked fields, and its transform alone (dct.hip)
+int dst_plan_create(bk_ctx* ctx, const int n[2], const double ainv[2], double c, int batch, DctPlan** out);
+int dst_transform(bk_ctx* ctx, DctPlan* p, int inverse, const double* in, double* out);
+const double* dst_plan_lam(const DctPlan* p, int axis);     // device table of the axis' eigenvalues, natural order
+double* dst_plan_scratch(const DctPlan* p);                 // total doubles the plan owns next to dst_transform's own scratch
+int dst_plan_last_path(const DctPlan* p, int axis);         // 1 matrix-core product, 0 one thread per output, 2 rocBLAS, -1 none yet
 // dot_blocks (optional): when the merged middle pass runs as the fused LDS kernel it also leaves the per-tile partial sums
 // of v . out (= sum over the spectrum of symbol * |v^|^2: the transforms are orthonormal) in ctx->d_partials and their count
 // in *dot_blocks; 0 = not available on this path

@@ -24,6 +24,7 @@
 //                      (B + az Sz)^2 = B^2 + 2 az B Sz + az^2 Sz^2.  HBM traffic = read v + read u +
 //                      write out = 24 B/point (16 B/point for the residual) + halo re-reads that hit
 //                      L2 because the blockIdx -> tile map keeps neighbouring tiles on one XCD.
+#include "cgl_pw.h"
 #include "launch_plan.h"
 #include "ops.h"
 
@@ -440,24 +441,21 @@ __global__ void __launch_bounds__(256) cgl_kernel(CglK P) {
     };
     const double d1 = lap(v1), d2 = lap(v2);
     const double x1 = v1[idx], x2 = v2[idx];
-    const double r = P.r, mu = P.mu, nu = P.nu, c3 = P.c3, c5 = P.c5;
+    const CglPar par{P.r, P.mu, P.nu, P.c3, P.c5, P.gamma};
     double o1, o2;
     if (P.mode == 0 || P.mode == 2) {
-        // closed-form Jacobian block of the nonlinearity: Jcgl, examples/cGL2d.jl:66-69 (mode 2: its transpose, the
-        // adjoint Jacobian of the Hopf machinery -- the Laplacian part is symmetric)
-        const double u1 = P.u[idx], u2 = P.u[idx + n];
-        const double ua = u1 * u1 + u2 * u2;
-        const double f1u = r - 2 * u1 * (c3 * u1 - mu * u2) - c3 * ua - 4 * c5 * ua * u1 * u1 - c5 * ua * ua;
-        const double f1v = -nu - 2 * u2 * (c3 * u1 - mu * u2) + mu * ua - 4 * c5 * ua * u1 * u2;
-        const double f2u = nu - 2 * u1 * (c3 * u2 + mu * u1) - mu * ua - 4 * c5 * ua * u1 * u2;
-        const double f2v = r - 2 * u2 * (c3 * u2 + mu * u1) - c3 * ua - 4 * c5 * ua * u2 * u2 - c5 * ua * ua;
+        // closed-form Jacobian block of the nonlinearity (cgl_pw.h: cgl_jac; mode 2: its transpose, the adjoint Jacobian of the
+        // Hopf machinery -- the Laplacian part is symmetric)
+        double f1u, f1v, f2u, f2v;
+        cgl_jac(par, P.u[idx], P.u[idx + n], f1u, f1v, f2u, f2v);
         o1 = d1 + f1u * x1 + (P.mode == 0 ? f1v : f2u) * x2;
         o2 = d2 + (P.mode == 0 ? f2u : f1v) * x1 + f2v * x2;
     } else {
-        // NL, examples/cGL2d.jl:24-40
-        const double ua = x1 * x1 + x2 * x2;
-        o1 = d1 + (r * x1 - nu * x2 - ua * (c3 * x1 - mu * x2) - c5 * ua * ua * x1 + P.gamma);
-        o2 = d2 + (r * x2 + nu * x1 - ua * (c3 * x2 + mu * x1) - c5 * ua * ua * x2);
+        // NL (cgl_pw.h: cgl_nl)
+        double n1, n2;
+        cgl_nl(par, x1, x2, n1, n2);
+        o1 = d1 + n1;
+        o2 = d2 + n2;
     }
     P.out[idx] = P.a0 * x1 + P.a1 * o1;
     P.out[idx + n] = P.a0 * x2 + P.a1 * o2;

@@ -923,6 +923,63 @@ int bk_normal_form_nd(bk_ctx* ctx, bk_problem* prob, const double* x, const doub
                       const double* const* zeta, const bk_gmres_opts* lsopts, bk_precond* pl, double* psi01,
                       double* const* psi2, double* coef, int* converged, int* itlinear);
 
+/* ------------------------------------------------------------------ periodic orbits, trapezoid rule --------
+ * The functional Trapeze of src/periodicorbit/PeriodicOrbitTrapeze.jl as examples/cGL2d.jl:166-260 uses it (jacobian =
+ * FullMatrixFree()), for BK_PDE_CGL2D on one rank; any other problem kind gets the error of the Hopf entries.  Orbit vector
+ * (:139-142): M slices of N = 2 n doubles on the device, slice i = [u1; u2], and the period entry T as ONE host scalar.  With
+ * K = M - 1, prev(0) = K - 1, prev(i) = i - 1:
+ *     G_i = u_i - u_prev(i) - (h / 2) (F(u_i) + F(u_prev(i))), i < K;   G_K = u_K - u_0;   G_T = <u - xpi, phi>.
+ * h = T (1 / M) on each of the M - 1 intervals (get_time_step of an integer TimeMesh, src/TimeMesh.jl:21): the entry called T
+ * is M / (M - 1) times the orbit's period, as in every guess and result of the reference.                                   */
+typedef struct bk_potrap bk_potrap;
+typedef struct {
+    int converged;
+    int niter;       /* operator applications (KrylovKit flavor) / iterations, as bk_gmres reports them */
+    double resnorm;
+} bk_solve_result;
+/* Trapeze(prob, phi, xpi, M, 2n) (:67-110): M >= 3.  The section is set by one of the two calls below.                      */
+int bk_potrap_create(bk_problem* prob, int M, bk_potrap** out);
+int bk_potrap_destroy(bk_potrap* h);
+/* phi, xpi: M N doubles each (the constructor's arguments, cGL2d.jl:177-181); copied.                                       */
+int bk_potrap_set_section(bk_potrap* h, const double* phi, const double* xpi);
+/* The section in force (trap.ϕ, trap.xπ, :67-110), copied into M N doubles each; an error before a section is set.          */
+int bk_potrap_get_section(bk_potrap* h, double* phi, double* xpi);
+/* po_residual! (:249-269) with po_residual_bare! (:272-287): out = G(u, T)[0 .. M N), *out_tail = the phase condition
+ * <u, phi> - <xpi, phi> (:262).  One marching pass: every slice's stencil is evaluated once, nothing but out is written, the
+ * phase dot rides in the same pass (deterministic).  Context option "potrap_chunks": 0 (default) = the chunk count follows
+ * the device's compute units, k > 0 = k chunks of the time axis (clamped to [1, M - 1]); out has the same bits for every
+ * chunk count.  out must not alias u.                                                                                        */
+int bk_potrap_residual(bk_potrap* h, const double* u, double T, const double* params, int nparams, double* out, double* out_tail);
+/* po_jvp! (:294-330): the cyclic part Jc (:362-386), the period column -(dT / M / 2) (F(u_i) + F(u_prev(i))) (:309-317), the
+ * closure du_K - du_0 and *out_tail = <du, phi> (:323).  One marching pass as above.  out must not alias u or du.           */
+int bk_potrap_jvp(bk_potrap* h, const double* u, double T, const double* params, int nparams, const double* du, double dT,
+                  double* out, double* out_tail);
+/* dG(u, T) as an operator handle with one host tail scalar (the FullMatrixFree Jacobian, :330): REFERENCES u.               */
+int bk_potrap_op_create(bk_potrap* h, const double* u, double T, const double* params, int nparams, bk_op** out);
+/* updatesection! (:665-681): xpi <- u, phi_i <- F(u_i) / M for every slice.                                                 */
+int bk_potrap_update_section(bk_potrap* h, const double* u, double T, const double* params, int nparams);
+/* d_p G(u, T) for params[ipar], analytic where the reference differences the functional (src/continuation/Palc.jl:239-240):
+ * rows i < K are -(h / 2) (dpF(u_i) + dpF(u_prev(i))), the closure row and the tail are zero.  out must not alias u.        */
+int bk_potrap_dparam(bk_potrap* h, const double* u, double T, const double* params, int nparams, int ipar, double* out);
+/* The space-time spectral preconditioner P = diag(A0, 1) in the place of the ILU of the assembled Jacobian (cGL2d.jl:209-213):
+ * A0 is the cyclic-plus-closure matrix above with every J_i replaced by L0 = Lap (x) I_2 + [[a, -b], [b, a]], the operator of
+ * bk_precond_cgl_create (a = r, b = nu: the linearisation at the trivial state).  Applied exactly: the DST-I of all 2 M fields,
+ * per sine mode the scalar complex cyclic bidiagonal system in time by one recurrence, the DST-I back.  bk_precond_apply and
+ * bk_precond_destroy work on it; the period must be set first.                                                               */
+int bk_precond_potrap_create(bk_potrap* h, double a, double b, bk_precond** out);
+/* h = T / M of the preconditioner.  Refuses, naming the sine mode, when min_k |1 - (h/2) mu_k| or min_k |1 - rho_k^(M-1)| is
+ * below 1e-8 (mu_k = a + lam_k + i b, rho_k = (1 + (h/2) mu_k) / (1 - (h/2) mu_k)): a mode that is Hopf-critical for (a, b) at
+ * this period makes A0 singular -- move a.  An error for a preconditioner of another kind.                                  */
+int bk_precond_potrap_set_period(bk_precond* pl, double T);
+/* Which kernel the transform passes of the LAST application dispatched to, as the dispatch itself recorded it, per axis (x, y):
+ * 1 the matrix-core product, 0 one thread per output, 2 rocBLAS (option dct_gemm), -1 no application yet.  A diagnostic
+ * (the reference has no counterpart).                                                                                        */
+int bk_precond_potrap_transform_paths(bk_precond* pl, int paths[2]);
+/* ONE GMRES on diag(A0^-1, 1) dG [x; x_tail] = [A0^-1 rhs; rhs_tail] (the linear solve of newton(poTrapMF, ...),
+ * cGL2d.jl:213-219): op from bk_potrap_op_create, pl from bk_precond_potrap_create.  x must not alias rhs.                   */
+int bk_potrap_solve(bk_ctx* ctx, bk_op* op, bk_precond* pl, const double* rhs, double rhs_tail, double* x, double* x_tail,
+                    const bk_gmres_opts* opts, bk_solve_result* result);
+
 #ifdef __cplusplus
 }
 #endif
