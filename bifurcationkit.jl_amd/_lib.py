@@ -270,6 +270,13 @@ SIGNATURES = {
     "bk_precond_potrap_transform_paths": (I, [VP, c_int_p]),
     "bk_potrap_get_section": (I, [VP, VP, VP]),
     "bk_potrap_solve": (I, [VP, VP, VP, VP, D, VP, c_double_p, C.POINTER(GmresOpts), C.POINTER(SolveResult)]),
+    "bk_potrap_ivp_march": (I, [VP, VP, D, c_double_p, I, VP, VP]),
+    "bk_precond_potrap_ivp_create": (I, [VP, D, D, D, C.POINTER(VP)]),
+    "bk_precond_potrap_ivp_transform_paths": (I, [VP, c_int_p]),
+    "bk_potrap_monodromy_create": (I, [VP, VP, D, c_double_p, I, D, D, C.POINTER(GmresOpts), C.POINTER(VP)]),
+    "bk_potrap_monodromy_solve": (I, [VP, VP, VP, c_int_p, c_int_p]),
+    "bk_potrap_monodromy_stats": (I, [VP, c_int_p, c_int_p, c_int_p, c_int_p]),
+    "bk_eig_krylovkit_lm": (I, [VP, VP, I, C.POINTER(EigOpts), c_double_p, c_double_p, VP, VP, SZ, c_int_p, c_int_p, c_int_p]),
 }
 
 _lib = None

@@ -70,15 +70,19 @@ struct ShiftInvertOp : bk_op {
 using namespace bk;
 using dense::cplx;
 
-// Krylov-Schur core on an operator `Aop`.  invert: Aop = (J - sigma)^-1, Ritz values are ordered by magnitude (:LM) and
-// mapped back by 1/mu + sigma; otherwise Aop = J itself and the order is by real part (:LR, EigKrylovKit's default use).
-static int eig_core(bk_ctx* ctx, bk_op* Aop, bool invert, int nev, const bk_eig_opts* eo, double* vals_re, double* vals_im,
+// Krylov-Schur core on an operator `Aop`.  kInvertLM: Aop = (J - sigma)^-1, Ritz values are ordered by magnitude (:LM), mapped
+// back by 1/mu + sigma and returned by decreasing real part; kLR: Aop = J itself, ordered and returned by real part (:LR,
+// EigKrylovKit's default use); kLM: Aop itself, ordered and returned by decreasing modulus, no back-transform (which = :LM, what
+// _check_floquet_options forces for Floquet work, src/periodicorbit/Floquet.jl:4-17).
+enum EigMode { kLR = 0, kInvertLM = 1, kLM = 2 };
+static int eig_core(bk_ctx* ctx, bk_op* Aop, EigMode mode, int nev, const bk_eig_opts* eo, double* vals_re, double* vals_im,
                     double* vecs, double* vecs_im, size_t ldvecs, int* nvals_out, int* nconv_out, int* napplied) {
     // one-shot start vector (bk_eig_set_start_vector): the x0 of KrylovKit.eigsolve(A, x0, ...) -- EigKrylovKit.x0,
     // src/EigSolver.jl:143,160; the reference's SH3dEig passes rand(N) (examples/SH3d.jl:109), which stays the default
     const double* x0 = ctx->eig_x0;
     ctx->eig_x0 = nullptr;
     bk_op& A = *Aop;
+    const bool invert = mode == kInvertLM, by_modulus = mode != kLR;
     const size_t n = A.n;
     int m = eo->krylovdim;
     if (m > kMaxBasis - 1) m = kMaxBasis - 1;
@@ -162,7 +166,7 @@ static int eig_core(bk_ctx* ctx, bk_op* Aop, bool invert, int nev, const bk_eig_
         }
         order.resize(meff);
         for (int i = 0; i < meff; ++i) order[i] = i;
-        if (invert) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return std::abs(mu[x]) > std::abs(mu[y]); });  // :LM
+        if (by_modulus) std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return std::abs(mu[x]) > std::abs(mu[y]); });  // :LM
         else std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return mu[x].real() > mu[y].real(); });              // :LR
         resid.assign(meff, 0.0);
         for (int jj = 0; jj < meff; ++jj) {
@@ -271,6 +275,7 @@ static int eig_core(bk_ctx* ctx, bk_op* Aop, bool invert, int nev, const bk_eig_
     for (int i = 0; i < nout; ++i) perm[i] = i;
     std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) {
         if (okv[x] != okv[y]) return okv[x] > okv[y];                 // converged first, NaNs last
+        if (mode == kLM) return okv[x] && std::abs(lam[x]) > std::abs(lam[y]);
         return okv[x] && lam[x].real() > lam[y].real();
     });
     for (int i = 0; i < nout; ++i) {
@@ -309,7 +314,7 @@ extern "C" int bk_eig_shiftinvert(bk_ctx* ctx, bk_op* J, int nev, const bk_eig_o
     ShiftInvertOp A;
     A.ctx = ctx; A.n = J->n; A.ntail = 0; A.ls = *lsopts; A.pl = pl;
     A.Js.ctx = ctx; A.Js.n = J->n; A.Js.ntail = 0; A.Js.J = J; A.Js.sigma = eo->sigma;
-    BK_TRY(eig_core(ctx, &A, true, nev, eo, vals_re, vals_im, vecs, vecs_im, ldvecs, nvals_out, nconv_out, nullptr));
+    BK_TRY(eig_core(ctx, &A, kInvertLM, nev, eo, vals_re, vals_im, vecs, vecs_im, ldvecs, nvals_out, nconv_out, nullptr));
     if (numops_out) *numops_out = A.solves;
     ctx->opts["eig_last_inner_ops"] = (double)A.inner_ops;     // diagnostics: bk_ctx_get_option
     return 0;
@@ -323,5 +328,15 @@ extern "C" int bk_eig_krylovkit(bk_ctx* ctx, bk_op* J, int nev, const bk_eig_opt
                                 int* numops_out) {
     if (!ctx || !J || !eo || !vals_re || !vals_im || nev < 1) return -1;
     if (J->ntail != 0) return set_error(ctx, "bk_eig_krylovkit: operator must be unbordered");
-    return eig_core(ctx, J, false, nev, eo, vals_re, vals_im, vecs, vecs_im, ldvecs, nvals_out, nconv_out, numops_out);
+    return eig_core(ctx, J, kLR, nev, eo, vals_re, vals_im, vecs, vecs_im, ldvecs, nvals_out, nconv_out, numops_out);
+}
+
+// EigKrylovKit with which = :LM: Krylov-Schur on the operator itself, Ritz values ordered by modulus, no back-transform; values
+// come back by decreasing modulus.  What FloquetQaD runs on the monodromy (src/periodicorbit/Floquet.jl:4-17, :59-85).
+extern "C" int bk_eig_krylovkit_lm(bk_ctx* ctx, bk_op* op, int nev, const bk_eig_opts* eo, double* vals_re, double* vals_im,
+                                   double* vecs, double* vecs_im, size_t ldvecs, int* nvals_out, int* nconv_out,
+                                   int* numops_out) {
+    if (!ctx || !op || !eo || !vals_re || !vals_im || nev < 1) return -1;
+    if (op->ntail != 0) return set_error(ctx, "bk_eig_krylovkit_lm: operator must be unbordered");
+    return eig_core(ctx, op, kLM, nev, eo, vals_re, vals_im, vecs, vecs_im, ldvecs, nvals_out, nconv_out, numops_out);
 }

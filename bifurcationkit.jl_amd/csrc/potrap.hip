@@ -32,19 +32,8 @@
 #include "common.h"
 #include "hopf_pw.h"
 #include "ops.h"
+#include "potrap_pw.h"
 #include "stream.h"
-
-struct bk_potrap {
-    bk_ctx* ctx = nullptr;
-    bk_problem* prob = nullptr;
-    int M = 0;
-    size_t n = 0;                  // grid points per field; a slice holds N = 2 n doubles
-    double* phi = nullptr;         // [M N] the normals of the section
-    double* xpi = nullptr;         // [M N] its reference point
-    double c0 = 0.0;               // <xpi, phi>
-    bool has_section = false;
-    size_t len() const { return 2 * n * (size_t)M; }
-};
 
 namespace bk {
 
@@ -63,22 +52,6 @@ struct PoK {
     const double* phi;
     double* out;
 };
-
-// One slice's values at a grid point: the centre pair and the 5-point Dirichlet Laplacian of both fields (cgl_kernel's lap)
-struct PoPoint { double c1, c2, d1, d2; };
-__device__ __forceinline__ PoPoint po_load(const PoK& P, const double* s, size_t n, size_t idx, int i, int j) {
-    auto lap = [&](const double* f, double c) {
-        const double w = i > 0 ? f[idx - 1] : 0.0, e = i + 1 < P.nx ? f[idx + 1] : 0.0;
-        const double so = j > 0 ? f[idx - P.nx] : 0.0, nn = j + 1 < P.ny ? f[idx + P.nx] : 0.0;
-        return P.ax * ((w + e) - 2.0 * c) + P.ay * ((so + nn) - 2.0 * c);
-    };
-    PoPoint q;
-    q.c1 = s[idx];
-    q.c2 = s[idx + n];
-    q.d1 = lap(s, q.c1);
-    q.d2 = lap(s + n, q.c2);
-    return q;
-}
 
 // Grid: blockIdx.x = chunk * ntiles + tile.  Rows [r0, r1) of the K = M - 1 cyclic rows; the walk starts one slice earlier
 // (t = -1: the predecessor of row r0, evaluated by the same code as every other slice and not stored, so a row's bits do not
@@ -196,6 +169,8 @@ __global__ void __launch_bounds__(kThreads) potrap_timesolve_kernel(PoTs P) {
     P.spec[(size_t)K * N + n + k] += w0.i;
 }
 
+}  // namespace
+
 // The chunk length of the marching kernels.  The spatial tiles alone are 4 workgroups at the example's 41 x 21 grid, so the K
 // rows are cut into chunks until about two workgroups per compute unit are in flight: nchunks = ceil(2 CUs / tiles) clamped to
 // [1, K], C = ceil(K / nchunks).  Context option "potrap_chunks" > 0 forces the chunk count (clamped the same way).
@@ -220,6 +195,8 @@ int potrap_params(bk_potrap* h, const double* params, int nparams, CglPar* par) 
     *par = CglPar{params[0], params[1], params[2], params[3], params[4], params[5]};
     return 0;
 }
+
+namespace {
 
 // the marching pass: out and the phase dot <x, phi> (x = u, or du for the JVP); algorithmic bytes: u (and du) read, out written,
 // phi read
@@ -304,8 +281,6 @@ struct PoTrapPrecOp : bk_op {
         return 0;
     }
 };
-
-constexpr double kPoPivot = 1e-8;      // the project's pivot threshold: a guard, not a tolerance
 
 }  // namespace
 }  // namespace bk

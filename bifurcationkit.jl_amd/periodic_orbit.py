@@ -6,6 +6,11 @@
   newton_po_trap             newton(poTrapMF, orbitguess_f, opt_po; normN = norminf)        :213-219
   continuation_po_trap       continuation(poTrapMF, outpo_f.u, PALC(), ...), secant tangent, BorderingBLS, updatesection every step
   get_periodic_orbit         :651-657
+  PoTrapMonodromy            MonodromyQaD_matrix_free(::Trapeze) as ONE space-time solve   src/periodicorbit/Floquet.jl:285-315
+  floquet_multipliers        compute_eigenvalues(::FloquetQaD, ...), which = :LM            Floquet.jl:59-85 (csrc/floquet.hip)
+  floquet_eigenfunction      Val(:ExtractEigenVector)                                        Floquet.jl:319-355
+  monodromy_sequential       the call-by-call mirror of :285-315 (yardstick and timing baseline)
+  classify_po_bifurcation    _get_bifurcation_type for a Floquet solver                      src/Bifurcations.jl:80-151
 
 An orbit is ``BorderedArray(u, T)``: ``u`` the M slices [u1; u2] on the device, ``T`` the period entry on the host.  The time step
 is h = T / M on each of the M - 1 intervals (src/TimeMesh.jl:21), so ``T`` is M / (M - 1) times the orbit's period -- the
@@ -271,11 +276,18 @@ def amplitude(u: HipVec) -> float:
 
 
 def continuation_po_trap(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params, lens, cp: Cn.ContinuationPar, ls: _GMRES,
-                         theta=0.5, update_section_every_step=1, verbosity=0):
+                         theta=0.5, update_section_every_step=1, verbosity=0, nev=0, detect_bifurcation=0, tol_stability=1e-10,
+                         eig=None):
     """PALC on the (N M + 1) + 1 system (continuation(poTrapMF, ..., PALC()) of cGL2d.jl:221-260): two Newton solves and the secant
     tangent, then per step newton_palc with BorderingBLS -- two preconditioned solves per Newton step, d_p G analytic --, the
     step-size control of continuation.py and updatesection! after every accepted step (the reference's default).  ``lens``: the
-    name or index of the continuation parameter.  Returns dict(p, T, amplitude, itnewton, itlinear, ds, orbit, converged)."""
+    name or index of the continuation parameter.  Returns dict(p, T, amplitude, itnewton, itlinear, ds, orbit, converged).
+
+    ``nev > 0``: at every recorded point the ``nev`` leading Floquet multipliers (``floquet_multipliers`` with the orbit
+    preconditioner's (a, b), ``eig``), recorded as ``floquet`` (the exponents), ``n_unstable`` (Re sigma > tol_stability), ``n_imag``
+    (the unstable ones with |Im sigma| > tol_stability) and ``stable``; ``detect_bifurcation >= 2`` adds ``specialpoints``: one
+    dict(step, interval, type, delta, ind_ev) whenever n_unstable changes between two points (``classify_po_bifurcation``; no
+    bisection).  With the defaults nothing of this runs."""
     params = [float(x) for x in params]
     ipar = po.prob.param_names.index(lens) if isinstance(lens, str) else int(lens)
     pl = _precond_for(po, ls, params).set_period(T)
@@ -299,11 +311,28 @@ def continuation_po_trap(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params,
         br["p"].append(z.p); br["T"].append(z.u.p); br["amplitude"].append(amplitude(z.u.u))
         br["itnewton"].append(sol.itnewton); br["itlinear"].append(it); br["ds"].append(ds); br["converged"].append(sol.converged)
 
+    if nev > 0:
+        br.update(floquet=[], n_unstable=[], n_imag=[], stable=[], eig_converged=[])
+        if detect_bifurcation >= 2:
+            br["specialpoints"] = []
+
+    def record_stability(z, step):
+        fl = floquet_multipliers(po, z.u.u, z.u.p, F.pv(z.p), nev, ls, eig=eig, a=pl.a, b=pl.b)
+        nu, ni = stability_counts(fl["exponents"], tol_stability)
+        if detect_bifurcation >= 2 and br["n_unstable"] and nu != br["n_unstable"][-1]:
+            tp = classify_po_bifurcation(nu, br["n_unstable"][-1], ni, br["n_imag"][-1])
+            if tp is not None:
+                br["specialpoints"].append(dict(step=step, interval=(br["p"][-2], br["p"][-1]), **tp))
+        br["floquet"].append(fl["exponents"]); br["n_unstable"].append(nu); br["n_imag"].append(ni); br["stable"].append(nu == 0)
+        br["eig_converged"].append(fl["converged"])
+
     ds = cp.ds
     tau = Cn.secant_tangent(z1, z0, ds, theta)
     z, z_old = z0.copy(), z0.copy()
     z_pred = z.copy().add_(tau, ds)
     record(z, s0, ds, list(lin.counts))
+    if nev > 0:
+        record_stability(z, 0)
     step = 0
     while step < cp.max_steps and (cp.p_min < z.p < cp.p_max or step == 0):
         before = len(lin.counts)
@@ -318,6 +347,8 @@ def continuation_po_trap(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params,
             z.copyto_(sol.u)
             step += 1
             record(z, sol, ds, lin.counts[before:])
+            if nev > 0:
+                record_stability(z, step)
         ds, stop = Cn.step_size_control(ds, sol.converged, sol.itnewton, cp)
         if stop:
             break
@@ -332,3 +363,201 @@ def get_periodic_orbit(po: PeriodicOrbitTrap, u: HipVec, T: float):
     """get_periodic_orbit (:651-657): (times, slices) with times = cumsum(T * [1 / M] * M) and slices of shape (M, N)."""
     times = np.cumsum(np.full(po.M, float(T) * (1.0 / po.M)))
     return times, u.numpy().reshape(po.M, po.N)
+
+
+# ------------------------------------------------------------------------------------------ Floquet multipliers
+class PoTrapMonodromy:
+    """dx -> MonodromyQaD_matrix_free(trap, u, par, dx) (src/periodicorbit/Floquet.jl:285-315) as an operator handle
+    (bk_potrap_monodromy_create): one space-time GMRES on the K = M - 1 slices of the initial-value system per application, in
+    the place of K slice solves one after another.  ``ls``: the GMRES options; ``(a, b)``: the preconditioner's constant-coefficient
+    operator, default a = r, b = nu.  Keeps ``u`` alive."""
+
+    def __init__(self, po: PeriodicOrbitTrap, u: HipVec, T: float, params, ls: _GMRES, a: float | None = None,
+                 b: float | None = None):
+        self.po, self.ctx, self.u, self.T, self.params = po, po.ctx, u, float(T), [float(x) for x in params]
+        self.a = self.params[0] if a is None else float(a)
+        self.b = self.params[2] if b is None else float(b)
+        o = ls._opts()
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.bk_potrap_monodromy_create(po.h, _ptr(u.t), self.T, _parr(self.params), len(self.params),
+                                                               self.a, self.b, C.byref(o), C.byref(h)), "bk_potrap_monodromy_create")
+        self.h = h
+
+    def _x(self, x: HipVec):
+        if x.n != self.po.N:
+            raise ValueError(f"the monodromy acts on one slice of N = {self.po.N} doubles")
+        return x
+
+    def __call__(self, x: HipVec, a0=0.0, a1=1.0) -> HipVec:
+        out = self._x(x).similar()
+        self.ctx.check(self.ctx.lib.bk_op_apply(self.h, _ptr(x.t), float(a0), float(a1), _ptr(out.t)), "bk_op_apply")
+        return out
+
+    def solve(self, x: HipVec):
+        """One application that returns all K slices -> (y_all (K N doubles), converged, niter); the monodromy applied to x is the
+        last slice."""
+        y = HipVec(self.ctx, self.ctx.empty(self.po.N * (self.po.M - 1)))
+        cv, it = C.c_int(), C.c_int()
+        self.ctx.check(self.ctx.lib.bk_potrap_monodromy_solve(self.h, _ptr(self._x(x).t), _ptr(y.t), C.byref(cv), C.byref(it)),
+                       "bk_potrap_monodromy_solve")
+        return y, bool(cv.value), it.value
+
+    def stats(self):
+        """dict(solves, failed, inner_its, paths) since creation; paths: the transform kernels of the last preconditioner
+        application per axis (PoTrapPreconditioner.transform_paths)."""
+        s, f, it, p = C.c_int(), C.c_int(), C.c_int(), (C.c_int * 2)()
+        self.ctx.check(self.ctx.lib.bk_potrap_monodromy_stats(self.h, C.byref(s), C.byref(f), C.byref(it), p),
+                       "bk_potrap_monodromy_stats")
+        return dict(solves=s.value, failed=f.value, inner_its=it.value, paths=(p[0], p[1]))
+
+    def __del__(self):
+        try:
+            if self.h.value:
+                self.ctx.lib.bk_op_destroy(self.h)
+        except Exception:
+            pass
+
+
+def ivp_march(po: PeriodicOrbitTrap, u: HipVec, T: float, params, y: HipVec, out: HipVec | None = None) -> HipVec:
+    """The initial-value operator of the monodromy on K slices (bk_potrap_ivp_march)."""
+    out = y.similar() if out is None else out
+    po.ctx.check(po.ctx.lib.bk_potrap_ivp_march(po.h, _ptr(u.t), float(T), _parr(params), len(params), _ptr(y.t), _ptr(out.t)),
+                 "bk_potrap_ivp_march")
+    return out
+
+
+class PoTrapIvpPreconditioner:
+    """A0^-1 of the initial-value system on K N doubles (bk_precond_potrap_ivp_create); the period is fixed at creation."""
+
+    def __init__(self, po: PeriodicOrbitTrap, a: float, b: float, T: float):
+        self.po, self.ctx = po, po.ctx
+        h = C.c_void_p()
+        self.ctx.check(self.ctx.lib.bk_precond_potrap_ivp_create(po.h, float(a), float(b), float(T), C.byref(h)),
+                       "bk_precond_potrap_ivp_create")
+        self.h = h
+
+    ldiv = PoTrapPreconditioner.ldiv
+    __del__ = PoTrapPreconditioner.__del__
+
+    def transform_paths(self):
+        p = (C.c_int * 2)()
+        self.ctx.check(self.ctx.lib.bk_precond_potrap_ivp_transform_paths(self.h, p), "bk_precond_potrap_ivp_transform_paths")
+        return p[0], p[1]
+
+
+def monodromy_sequential(po: PeriodicOrbitTrap, u: HipVec, T: float, params, x: HipVec, ls: _GMRES, a: float | None = None,
+                         b: float | None = None):
+    """The call-by-call mirror of MonodromyQaD_matrix_free(::Trapeze) (Floquet.jl:285-315): per step out <- out + (h / 2) J_prev out
+    (bk_jacobian, bk_op_apply with (1, h / 2)), then the slice solve (I - (h / 2) J_i) res = out (bk_gmres with a0 = 1, a1 = -h / 2,
+    the options of ``ls``).  Left preconditioner bk_precond_cgl_create(a - 2 / h, b): (L0 - 2 / h)^-1 = -(h / 2) (I - (h / 2) L0)^-1,
+    the slice preconditioner up to the factor -2 / h on the right-hand side, which the library applies to both sides of the solve.
+    The parity yardstick and the timing baseline of PoTrapMonodromy, not a product path.  Returns (out, inner iterations summed,
+    all converged)."""
+    from .hip import CGLBlockPreconditioner, HipJacobian
+    params = [float(v) for v in params]
+    prob, N, K = po.prob, po.N, po.M - 1
+    h = float(T) * (1.0 / po.M)
+    a = params[0] if a is None else a
+    b = params[2] if b is None else b
+    sl = [HipVec(po.ctx, u.t[i * N:(i + 1) * N], prob.nglobal) for i in range(K)]
+    o = ls._opts()
+    pl = CGLBlockPreconditioner(prob, a - 2.0 / h, b)
+    out, its, ok = x, 0, True
+    lib, ctx = po.ctx.lib, po.ctx
+    for i in range(K):
+        out = HipJacobian(prob, sl[K - 1 if i == 0 else i - 1], params)(out, 1.0, h / 2.0)
+        Ji = HipJacobian(prob, sl[i], params)
+        res = out.similar()
+        cv, it, rn = C.c_int(), C.c_int(), C.c_double()
+        ctx.check(lib.bk_gmres(ctx.h, Ji.h, _ptr(out.t), _ptr(res.t), 1.0, -h / 2.0, C.byref(o), pl.h, C.byref(cv), C.byref(it),
+                               C.byref(rn)), "bk_gmres")
+        its += it.value
+        ok = ok and bool(cv.value)
+        out = res
+    return out, its, ok
+
+
+def floquet_multipliers(po: PeriodicOrbitTrap, u: HipVec, T: float, params, nev: int, ls: _GMRES, eig=None, a: float | None = None,
+                        b: float | None = None, mono: PoTrapMonodromy | None = None):
+    """compute_eigenvalues(::FloquetQaD, ...) (Floquet.jl:59-85) on the matrix-free monodromy: Krylov-Schur with which = :LM
+    (bk_eig_krylovkit_lm; ``eig``: an EigKrylovKit whose tol, maxiter, krylovdim, seed and x0 are used; default tol 1e-8, krylovdim
+    20).  Returns dict(multipliers, exponents, vectors, converged, numops, inner_its): exponents = log(complex(mu)) sorted by
+    decreasing real part (:74-79), multipliers and vectors ((re, im) pairs) in the same order; a value that did not converge is
+    NaN.  Warns where a multiplier is infinite or NaN."""
+    import warnings
+
+    from .hip import EigKrylovKit
+    mono = PoTrapMonodromy(po, u, T, params, ls, a, b) if mono is None else mono
+    eig = EigKrylovKit(tol=1e-8, maxiter=20, krylovdim=20) if eig is None else eig
+    ctx, n = po.ctx, po.N
+    if eig.x0 is not None:
+        ctx.check(ctx.lib.bk_eig_set_start_vector(ctx.h, _ptr(eig.x0.t)), "bk_eig_set_start_vector")
+    kd = min(eig.krylovdim, 63, n - 1)
+    nev = min(int(nev), kd)
+    eo = L.EigOpts(0.0, int(kd), int(eig.maxiter), float(eig.tol), 0, int(eig.seed))
+    re, im = (C.c_double * (nev + 1))(), (C.c_double * (nev + 1))()
+    ld = (n + 31) // 32 * 32
+    vr, vi = ctx.empty(ld * (nev + 1)), ctx.empty(ld * (nev + 1))
+    nvals, nconv, nops = C.c_int(), C.c_int(), C.c_int()
+    before = mono.stats()["inner_its"]
+    ctx.check(ctx.lib.bk_eig_krylovkit_lm(ctx.h, mono.h, nev, C.byref(eo), re, im, _ptr(vr), _ptr(vi), ld, C.byref(nvals),
+                                          C.byref(nconv), C.byref(nops)), "bk_eig_krylovkit_lm")
+    m = nvals.value
+    vals = np.array([complex(re[i], im[i]) for i in range(m)])
+    if not np.all(np.isfinite(vals)):
+        warnings.warn("Detecting infinite or NaN eigenvalue during the computation of Floquet coefficients.")
+    sigma = floquet_exponents(vals)
+    order = _exponent_order(sigma)
+    vecs = [(HipVec(ctx, vr[i * ld:i * ld + n]), HipVec(ctx, vi[i * ld:i * ld + n])) for i in order]
+    return dict(multipliers=vals[order], exponents=sigma[order], vectors=vecs, converged=nconv.value >= nev, numops=nops.value,
+                inner_its=mono.stats()["inner_its"] - before, monodromy=mono)
+
+
+def floquet_exponents(mults):
+    """log.(complex.(vals)) (Floquet.jl:75), unsorted; log(0) = -inf."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.log(np.asarray(mults, dtype=complex))
+
+
+def _exponent_order(sigma):
+    """sortperm(logvals, by = real, rev = true) (Floquet.jl:76), NaN last."""
+    key = np.where(np.isnan(sigma.real), -np.inf, sigma.real)
+    return [int(i) for i in np.argsort(-key, kind="stable")]
+
+
+def floquet_eigenfunction(mono: PoTrapMonodromy, zeta):
+    """The space-time eigenfunction of a Floquet eigenvector (Val(:ExtractEigenVector), Floquet.jl:319-355): the K slices of the
+    solve that applies the monodromy to ``zeta``; a ``(re, im)`` pair gives a pair.  Slices are numbered as the reference numbers
+    them: the last one is mu zeta."""
+    if isinstance(zeta, (tuple, list)):
+        return tuple(mono.solve(z)[0] if z is not None else None for z in zeta)
+    return mono.solve(zeta)[0]
+
+
+def stability_counts(exponents, tol_stability):
+    """(n_unstable, n_imag): the exponents with Re sigma > tol_stability, and those of them with |Im sigma| > tol_stability
+    (NaN entries are ignored, as is_stable ignores them)."""
+    s = np.asarray(exponents, dtype=complex)
+    s = s[~np.isnan(s.real)]
+    un = s[s.real > tol_stability]
+    return int(un.size), int(np.sum(np.abs(un.imag) > tol_stability))
+
+
+def classify_po_bifurcation(n_unstable, n_unstable_prev, n_imag, n_imag_prev):
+    """_get_bifurcation_type (src/Bifurcations.jl:80-151) for a Floquet solver, from the stability counts of two consecutive points:
+    None when n_unstable did not change, else dict(type, delta, ind_ev) with type "bp" (one real exponent crosses), "pd" (one, with
+    a nonzero imaginary part: the multiplier crosses at -1), "ns" (a pair) or "nd" (anything else, a missing conjugate -- fewer
+    crossings than new imaginary parts --, or counts not yet populated, < 0).  Pure: needs no device."""
+    du, di = abs(n_unstable - n_unstable_prev), abs(n_imag - n_imag_prev)
+    if du == 0 and not du < di:
+        return None
+    if du == 1:
+        tp = "bp" if di == 0 else ("pd" if di == 1 else "nd")
+    elif du == 2:
+        tp = "ns" if di == 2 else "nd"
+    else:
+        tp = "nd"
+    if du < di or n_unstable * n_unstable_prev < 0 or n_imag * n_imag_prev < 0:
+        tp = "nd"
+    return dict(type=tp, delta=(n_unstable - n_unstable_prev, n_imag - n_imag_prev),
+                ind_ev=n_unstable_prev if n_unstable < n_unstable_prev else n_unstable)

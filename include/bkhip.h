@@ -980,6 +980,41 @@ int bk_precond_potrap_transform_paths(bk_precond* pl, int paths[2]);
 int bk_potrap_solve(bk_ctx* ctx, bk_op* op, bk_precond* pl, const double* rhs, double rhs_tail, double* x, double* x_tail,
                     const bk_gmres_opts* opts, bk_solve_result* result);
 
+/* ------------------------------------------------------------------ Floquet multipliers of trapezoid orbits --------
+ * The matrix-free monodromy of FloquetQaD (src/periodicorbit/Floquet.jl:48-85), MonodromyQaD_matrix_free(::Trapeze, ...)
+ * (:285-315): K = M - 1 sequential steps x <- (I - hh J_i)^-1 (I + hh J_prev(i)) x, hh = T (1 / M) / 2.  Here the same vector is
+ * the last slice of ONE block lower-bidiagonal initial-value system over all K slices,
+ *     A_i y_i - B_{i-1} y_{i-1} = 0 (i >= 1),  A_0 y_0 = B_{K-1} x,  A_i = I - hh J_i,  B_i = I + hh J_i,  M x = y_{K-1},
+ * solved by one left-preconditioned GMRES.  BK_PDE_CGL2D on one rank, as the other bk_potrap_* entries.                     */
+/* The initial-value operator on K slices y (K N doubles): out_0 = y_0 - hh J_0 y_0, out_i = (y_i - hh J_i y_i) - (y_{i-1} +
+ * hh J_{i-1} y_{i-1}), J_i the cGL Jacobian at orbit slice i of u (M N doubles).  One marching pass; option "potrap_chunks" as
+ * for bk_potrap_residual, the same bits for every chunk count.  out must not alias y or u.                                  */
+int bk_potrap_ivp_march(bk_potrap* h, const double* u, double T, const double* params, int nparams, const double* y, double* out);
+/* The preconditioner of that system on K N doubles: every J_i replaced by L0 = Lap (x) I_2 + [[a, -b], [b, a]], applied exactly
+ * (DST-I of all 2 K fields, per sine mode w_i = rho w_{i-1} + f_i / alpha from w_{-1} = 0, DST-I back; alpha, rho as in
+ * bk_precond_potrap_set_period).  The period is fixed at creation.  Refuses, naming the sine mode, when min_k |alpha_k| is below
+ * 1e-8.  bk_precond_apply and bk_precond_destroy work on it.                                                                 */
+int bk_precond_potrap_ivp_create(bk_potrap* h, double a, double b, double T, bk_precond** out);
+/* As bk_precond_potrap_transform_paths, for a preconditioner of bk_precond_potrap_ivp_create.                               */
+int bk_precond_potrap_ivp_transform_paths(bk_precond* pl, int paths[2]);
+/* dx -> MonodromyQaD_matrix_free(trap, u0, par, dx) (Floquet.jl:63, :285-315) as an unbordered operator of length N:
+ * apply(x, a0, a1, out) = a0 x + a1 y_{K-1}, one GMRES (opts: a GMRES flavor, left preconditioner (a, b) only) per application.
+ * A solve that does not converge is counted, not fatal.  REFERENCES u; owns its preconditioner and work vectors; destroy with
+ * bk_op_destroy.                                                                                                             */
+int bk_potrap_monodromy_create(bk_potrap* h, const double* u, double T, const double* params, int nparams, double a, double b,
+                               const bk_gmres_opts* opts, bk_op** out);
+/* One application that also returns all K slices y_0 .. y_{K-1} (K N doubles): for a Floquet eigenvector x the space-time
+ * eigenfunction of the Val(:ExtractEigenVector) method (Floquet.jl:319-355), out of the same solve.                          */
+int bk_potrap_monodromy_solve(bk_op* op, const double* x, double* y_all, int* converged, int* niter);
+/* Counters since creation: solves, those that did not converge, GMRES iterations summed; paths: the transform kernels of the
+ * last preconditioner application (bk_precond_potrap_transform_paths).  Any pointer may be NULL.                             */
+int bk_potrap_monodromy_stats(bk_op* op, int* solves, int* failed, int* inner_its, int paths[2]);
+/* (eig::EigKrylovKit)(op, nev) with which = :LM, what _check_floquet_options forces for Floquet work (Floquet.jl:4-17):
+ * Krylov-Schur on the operator itself, Ritz values ordered by modulus, no back-transform; values come back by decreasing
+ * modulus.  Arguments and output conventions of bk_eig_krylovkit (sigma ignored).                                            */
+int bk_eig_krylovkit_lm(bk_ctx* ctx, bk_op* op, int nev, const bk_eig_opts* eopts, double* vals_re, double* vals_im,
+                        double* vecs, double* vecs_im, size_t ldvecs, int* nvals, int* nconv, int* numops);
+
 #ifdef __cplusplus
 }
 #endif
