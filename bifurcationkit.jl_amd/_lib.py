@@ -270,6 +270,19 @@ SIGNATURES = {
     "bk_precond_potrap_transform_paths": (I, [VP, c_int_p]),
     "bk_potrap_get_section": (I, [VP, VP, VP]),
     "bk_potrap_solve": (I, [VP, VP, VP, VP, D, VP, c_double_p, C.POINTER(GmresOpts), C.POINTER(SolveResult)]),
+    "bk_potrap_jvp_adjoint": (I, [VP, VP, D, c_double_p, I, VP, D, VP, c_double_p]),
+    "bk_potrap_op_adjoint_create": (I, [VP, VP, D, c_double_p, I, C.POINTER(VP)]),
+    "bk_precond_potrap_adjoint_create": (I, [VP, D, D, C.POINTER(VP)]),
+    "bk_potrap_bordered_solve": (I, [VP, VP, VP, VP, D, VP, D, D, VP, D, D, VP, c_double_p, c_double_p, C.POINTER(GmresOpts),
+                                     C.POINTER(SolveResult)]),
+    "bk_potrap_fold_border": (I, [VP, VP, D, c_double_p, I, I, VP, D, VP, VP, c_double_p, c_double_p]),
+    "bk_potrap_fold_terms": (I, [VP, VP, D, c_double_p, I, VP, D, VP, D, VP, VP, C.POINTER(GmresOpts), VP, c_double_p, VP,
+                                 c_double_p, c_double_p, c_int_p, c_int_p]),
+    "bk_potrap_fold_linsolve": (I, [VP, VP, D, c_double_p, I, I, VP, D, VP, VP, I, C.POINTER(VP), c_double_p, c_double_p,
+                                    C.POINTER(GmresOpts), C.POINTER(VP), c_double_p, c_double_p, c_int_p, c_int_p]),
+    "bk_potrap_newton_fold": (I, [VP, VP, c_double_p, c_double_p, c_double_p, I, I, VP, D, VP, D, VP, VP, C.POINTER(NewtonOpts),
+                                  C.POINTER(GmresOpts), VP, c_double_p, VP, c_double_p, c_double_p, C.POINTER(NewtonResult),
+                                  c_int_p]),
     "bk_potrap_ivp_march": (I, [VP, VP, D, c_double_p, I, VP, VP]),
     "bk_precond_potrap_ivp_create": (I, [VP, D, D, D, C.POINTER(VP)]),
     "bk_precond_potrap_ivp_transform_paths": (I, [VP, c_int_p]),

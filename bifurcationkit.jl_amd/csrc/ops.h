@@ -326,6 +326,10 @@ int bls_matrixfree_pl(bk_ctx* ctx, bk_op* J, int m, const double* const* a, cons
 // it (cshift.hip: ComplexShiftOp; delete `*out` after the solve).  order 0: a0 + a1 Pl^-1 J, order 1: Pl^-1 (a0 + a1 J); tmp: J->n
 // doubles owned by the caller.
 int cshift_op_create(bk_ctx* ctx, bk_op* J, bk_precond* pl, double a0r, double a0i, double a1, int order, double* tmp, bk_op** out);
+// y += sum_j coef[j] atil[j], dots[j] = <b[j], x> (all-reduced), j < m <= BK_MAX_BORDER, one pass (bordered.hip:
+// bordered_tail_kernel); y must not alias any other operand
+int bordered_tail(bk_ctx* ctx, size_t n, int m, double* y, const double* x, const double* const* atil, const double* const* b,
+                  const double* coef, double* dots);
 // y += xi atil, d = b^H x on (re, im) pairs of length n (bordered.hip: cbordered_tail_kernel); coef = (Re xi, Im xi), dots = (Re d,
 // Im d); yr, yi must not alias each other or any other operand
 int cbordered_tail(bk_ctx* ctx, size_t n, double* yr, double* yi, const double* xr, const double* xi, const double* atr,

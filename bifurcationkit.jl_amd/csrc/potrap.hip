@@ -225,16 +225,19 @@ int potrap_check(bk_potrap* h, const char* who, bool need_section) {
     return 0;
 }
 
-// dG(u, T) as an operator on (device vector of M N doubles, host tail dT); references u
+// dG(u, T), or its transpose (adjoint: the pass of pofold.hip), as an operator on (device vector of M N doubles, host tail dT);
+// references u
 struct PoTrapOp : bk_op {
     bk_potrap* h = nullptr;
     const double* u = nullptr;
     double T = 0.0;
     CglPar par{};
+    bool adjoint = false;
     int apply(const double* x, const double* xt, double a0, double a1, double* out, double* outt) override {
         if (out == x) return set_error(ctx, "potrap operator: out must not alias x");
         double dot = 0.0;
-        BK_TRY(potrap_march(h, par, u, T, x, xt[0], out, &dot));
+        if (adjoint) BK_TRY(potrap_adjoint_march(h, par, u, T, x, xt[0], out, &dot));
+        else BK_TRY(potrap_march(h, par, u, T, x, xt[0], out, &dot));
         if (!(a0 == 0.0 && a1 == 1.0)) BK_TRY(v_axpby(ctx, n, a0, x, a1, out));
         outt[0] = a0 * xt[0] + a1 * dot;
         return 0;
@@ -243,19 +246,23 @@ struct PoTrapOp : bk_op {
 
 // P = diag(A0, 1): A0 = the cyclic-plus-closure matrix above with every J_i replaced by L0 = Lap (x) I_2 + [[a, -b], [b, a]], the
 // operator bk_precond_cgl_create inverts.  The DST-I of all 2 M fields in one batched plan diagonalises the Laplacian; per mode
-// what is left is the scalar complex system potrap_timesolve_kernel solves.
+// what is left is the scalar complex system potrap_timesolve_kernel solves.  adjoint: diag(A0^T, 1) -- the DST-I is symmetric, so
+// only the time solve differs (pofold.hip).
 struct PoTrapPrecond : bk_precond {
     DctPlan* plan = nullptr;
     int nx = 0, ny = 0, M = 0;
     double a = 0.0, b = 0.0, hh = 0.0;
     bool period_set = false;
+    bool adjoint = false;
     std::vector<double> lx, ly;    // host copies of the eigenvalue tables (the guards of set_period)
     ~PoTrapPrecond() override { dct_plan_destroy(plan); }
     int apply(const double* v, double* out) override {
         if (!period_set) return set_error(ctx, "potrap preconditioner: no period set (bk_precond_potrap_set_period first)");
         double* spec = dst_plan_scratch(plan);
         BK_TRY(dst_transform(ctx, plan, 0, v, spec));
-        {
+        if (adjoint) {
+            BK_TRY(potrap_adjoint_timesolve(ctx, nx, ny, M, a, b, hh, dst_plan_lam(plan, 0), dst_plan_lam(plan, 1), spec));
+        } else {
             const size_t npts = (size_t)nx * ny;
             ProfScope ps(ctx, "potrap_timesolve", 8.0 * n * 3);
             const PoTs P{nx, ny, M, a, b, hh, dst_plan_lam(plan, 0), dst_plan_lam(plan, 1), spec};
@@ -283,6 +290,19 @@ struct PoTrapPrecOp : bk_op {
 };
 
 }  // namespace
+
+int potrap_pair_check(bk_ctx* ctx, const char* who, bk_op* op, bk_precond* pl) {
+    PoTrapOp* pop = dynamic_cast<PoTrapOp*>(op);
+    if (!pop) return set_error(ctx, "%s: op is not an operator of bk_potrap_op_create", who);
+    PoTrapPrecond* ppl = dynamic_cast<PoTrapPrecond*>(pl);
+    if (!ppl || pl->n != op->n) return set_error(ctx, "%s: pl is not a preconditioner of bk_precond_potrap_create for this orbit", who);
+    if (pop->adjoint != ppl->adjoint)
+        return set_error(ctx, "%s: %s operator with %s preconditioner (pair bk_potrap_op_adjoint_create with "
+                              "bk_precond_potrap_adjoint_create)", who, pop->adjoint ? "an adjoint" : "a forward",
+                         ppl->adjoint ? "an adjoint" : "a forward");
+    return 0;
+}
+
 }  // namespace bk
 
 using namespace bk;
@@ -356,16 +376,24 @@ int bk_potrap_jvp(bk_potrap* h, const double* u, double T, const double* params,
     return potrap_march(h, par, u, T, du, dT, out, out_tail);
 }
 
-int bk_potrap_op_create(bk_potrap* h, const double* u, double T, const double* params, int nparams, bk_op** out) {
+static int potrap_op_create(bk_potrap* h, const double* u, double T, const double* params, int nparams, bool adjoint, bk_op** out) {
     if (!h || !u || !params || !out) return -1;
     CglPar par;
     BK_TRY(potrap_params(h, params, nparams, &par));
-    BK_TRY(potrap_check(h, "bk_potrap_op_create", true));
+    BK_TRY(potrap_check(h, adjoint ? "bk_potrap_op_adjoint_create" : "bk_potrap_op_create", true));
     PoTrapOp* op = new PoTrapOp();
     op->ctx = h->ctx; op->n = h->len(); op->ntail = 1;
-    op->h = h; op->u = u; op->T = T; op->par = par;
+    op->h = h; op->u = u; op->T = T; op->par = par; op->adjoint = adjoint;
     *out = op;
     return 0;
+}
+
+int bk_potrap_op_create(bk_potrap* h, const double* u, double T, const double* params, int nparams, bk_op** out) {
+    return potrap_op_create(h, u, T, params, nparams, false, out);
+}
+
+int bk_potrap_op_adjoint_create(bk_potrap* h, const double* u, double T, const double* params, int nparams, bk_op** out) {
+    return potrap_op_create(h, u, T, params, nparams, true, out);
 }
 
 int bk_potrap_update_section(bk_potrap* h, const double* u, double T, const double* params, int nparams) {
@@ -402,11 +430,11 @@ int bk_potrap_dparam(bk_potrap* h, const double* u, double T, const double* para
     return 0;
 }
 
-int bk_precond_potrap_create(bk_potrap* h, double a, double b, bk_precond** out) {
+static int potrap_precond_create(bk_potrap* h, double a, double b, bool adjoint, bk_precond** out) {
     if (!h || !out) return -1;
     bk_ctx* ctx = h->ctx;
     PoTrapPrecond* P = new PoTrapPrecond();
-    P->ctx = ctx; P->n = h->len();
+    P->ctx = ctx; P->n = h->len(); P->adjoint = adjoint;
     P->nx = h->prob->desc.n[0]; P->ny = h->prob->desc.n[1]; P->M = h->M; P->a = a; P->b = b;
     const int s = dst_plan_create(ctx, h->prob->desc.n, h->prob->ainv, 0.0, 2 * h->M, &P->plan);
     if (s != 0) { delete P; return s; }
@@ -419,6 +447,12 @@ int bk_precond_potrap_create(bk_potrap* h, double a, double b, bk_precond** out)
     }
     *out = P;
     return 0;
+}
+
+int bk_precond_potrap_create(bk_potrap* h, double a, double b, bk_precond** out) { return potrap_precond_create(h, a, b, false, out); }
+
+int bk_precond_potrap_adjoint_create(bk_potrap* h, double a, double b, bk_precond** out) {
+    return potrap_precond_create(h, a, b, true, out);
 }
 
 int bk_precond_potrap_set_period(bk_precond* pl, double T) {
@@ -466,9 +500,7 @@ int bk_precond_potrap_transform_paths(bk_precond* pl, int paths[2]) {
 int bk_potrap_solve(bk_ctx* ctx, bk_op* op, bk_precond* pl, const double* rhs, double rhs_tail, double* x, double* x_tail,
                     const bk_gmres_opts* opts, bk_solve_result* result) {
     if (!ctx || !op || !pl || !rhs || !x || !x_tail || !opts || !result) return -1;
-    if (!dynamic_cast<PoTrapOp*>(op)) return set_error(ctx, "bk_potrap_solve: op is not an operator of bk_potrap_op_create");
-    if (!dynamic_cast<PoTrapPrecond*>(pl) || pl->n != op->n)
-        return set_error(ctx, "bk_potrap_solve: pl is not a preconditioner of bk_precond_potrap_create for this orbit");
+    BK_TRY(potrap_pair_check(ctx, "bk_potrap_solve", op, pl));
     if (opts->flavor >= BK_KRYLOV_MINRES) return set_error(ctx, "bk_potrap_solve: the orbit Jacobian is not symmetric (use a GMRES flavor)");
     if (opts->pr) return set_error(ctx, "bk_potrap_solve: left preconditioner only");
     if (x == rhs) return set_error(ctx, "bk_potrap_solve: x must not alias rhs");

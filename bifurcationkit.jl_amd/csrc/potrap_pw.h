@@ -1,6 +1,6 @@
 // What the marching kernels of the trapezoid periodic-orbit functional (potrap.hip) and of the monodromy's initial-value system
-// (floquet.hip) share: the handle, one slice's stencil load, the chunk rule and the parameter check.  The pointwise Jacobian block
-// (cgl_jac) is in cgl_pw.h.
+// (floquet.hip) and of the adjoint (pofold.hip) share: the handle, one slice's stencil load, the chunk rule and the parameter
+// check.  The pointwise Jacobian block (cgl_jac) is in cgl_pw.h.
 // Internal header.
 #pragma once
 #include "cgl_pw.h"
@@ -44,5 +44,15 @@ constexpr double kPoPivot = 1e-8;      // the project's pivot threshold: a guard
 // potrap.hip
 int potrap_chunking(bk_ctx* ctx, size_t n, int M, unsigned* ntiles, int* C, int* nchunks);
 int potrap_params(bk_potrap* h, const double* params, int nparams, CglPar* par);
+
+// "who: ..." unless op and pl are an orbit operator and an orbit preconditioner of the same length and the same kind (both
+// forward or both adjoint)
+int potrap_pair_check(bk_ctx* ctx, const char* who, bk_op* op, bk_precond* pl);
+
+// pofold.hip: the first M N entries and the tail of dG(u, T)^T (w, tau), and the time solve of A0^-T on a spectrum in place
+int potrap_adjoint_march(bk_potrap* h, const CglPar& par, const double* u, double T, const double* w, double tau, double* out,
+                         double* tail);
+int potrap_adjoint_timesolve(bk_ctx* ctx, int nx, int ny, int M, double a, double b, double hh, const double* lx, const double* ly,
+                             double* spec);
 
 }  // namespace bk

@@ -518,16 +518,8 @@ __global__ void __launch_bounds__(256) dparam_kernel(DpK P) {
             P.out[i] = P.c * (P.ipar == 0 ? u : u * u * u);
         } else {                                        // cGL, params (r, mu, nu, c3, c5, gamma): examples/cGL2d.jl:24-40
             const double u1 = P.u[i], u2 = P.u[i + P.n];
-            const double ua = u1 * u1 + u2 * u2;
             double o1, o2;
-            switch (P.ipar) {
-                case 0: o1 = u1; o2 = u2; break;
-                case 1: o1 = ua * u2; o2 = -ua * u1; break;
-                case 2: o1 = -u2; o2 = u1; break;
-                case 3: o1 = -ua * u1; o2 = -ua * u2; break;
-                case 4: o1 = -ua * ua * u1; o2 = -ua * ua * u2; break;
-                default: o1 = 1.0; o2 = 0.0; break;
-            }
+            cgl_dpar(P.ipar, u1, u2, o1, o2);
             P.out[i] = P.c * o1;
             P.out[i + P.n] = P.c * o2;
         }

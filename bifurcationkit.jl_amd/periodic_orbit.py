@@ -3,6 +3,12 @@
   PeriodicOrbitTrap          Trapeze(prob, phi, xpi, M, 2n; jacobian = FullMatrixFree())   src/periodicorbit/PeriodicOrbitTrapeze.jl
   PoTrapPreconditioner       the space-time spectral preconditioner diag(A0, 1) in the place of the example's ILU (:209-213)
   po_guess_from_hopf         the guess of :172-174 and the section of :177-181 from predictor(hopf, ds)
+  PoTrapJacobian.adjoint     dG^T, with PoTrapPreconditioner(adjoint=True) the left-null-vector solves of MinAugFold.jl:15-69
+  po_bordered_solve          ONE GMRES on [dG a; b' c] (or dG^T), regular at a fold of limit cycles
+  po_fold_terms              the bordered vectors v, w and sigma of the fold of orbits         MinAugFold.jl:15-69
+  newton_fold_po[_native]    newton_fold(br_po, indfold; prob = probFold) on bordered solves    cGL2d.jl:347-370
+  po_fold_point              fold_point(br_po, indfold) and the a = b = tangent of newton_fold  cGL2d.jl:354, MinAugFold.jl:244-247
+  PoFoldProblem, PoFoldLinearSolverMinAug, continuation_fold_po   continuation_fold(probFold, br_po, indfold, c5)   cGL2d.jl:381-392
   newton_po_trap             newton(poTrapMF, orbitguess_f, opt_po; normN = norminf)        :213-219
   continuation_po_trap       continuation(poTrapMF, outpo_f.u, PALC(), ...), secant tangent, BorderingBLS, updatesection every step
   get_periodic_orbit         :651-657
@@ -16,7 +22,7 @@ An orbit is ``BorderedArray(u, T)``: ``u`` the M slices [u1; u2] on the device, 
 is h = T / M on each of the M - 1 intervals (src/TimeMesh.jl:21), so ``T`` is M / (M - 1) times the orbit's period -- the
 reference's convention, kept.  Newton and PALC are the ones of ``continuation.py`` (``newton``, ``newton_palc``, ``secant_tangent``,
 ``step_size_control``), run on this functional.  The hot path -- functional, Jacobian-vector product, preconditioner, GMRES -- is
-``csrc/potrap.hip``.
+``csrc/potrap.hip``; the adjoint pass and the transposed time solve are ``csrc/pofold.hip``.
 """
 from __future__ import annotations
 
@@ -94,6 +100,22 @@ class PeriodicOrbitTrap:
                                                   _ptr(out.t), C.byref(tail)), "bk_potrap_jvp")
         return BorderedArray(out, tail.value)
 
+    def jvp_adjoint(self, u: HipVec, T: float, params, w: HipVec, tau: float) -> BorderedArray:
+        """dG(u, T)^T (w, tau) (bk_potrap_jvp_adjoint)."""
+        out, tail = u.similar(), C.c_double()
+        self.ctx.check(self.ctx.lib.bk_potrap_jvp_adjoint(self.h, _ptr(u.t), float(T), _parr(params), len(params), _ptr(w.t),
+                                                          float(tau), _ptr(out.t), C.byref(tail)), "bk_potrap_jvp_adjoint")
+        return BorderedArray(out, tail.value)
+
+    def fold_border(self, u: HipVec, T: float, params, ipar: int, v: BorderedArray, w: HipVec):
+        """The border row of the fold system and sigma_p for params[ipar] (bk_potrap_fold_border) ->
+        (BorderedArray(sigma_x, (sigma_x)_T), sigma_p): <sigma_x, X> = -<w, d2G[v, X]>, sigma_p = -<w, d_p(dG) v>."""
+        out, st, sp = u.similar(), C.c_double(), C.c_double()
+        self.ctx.check(self.ctx.lib.bk_potrap_fold_border(self.h, _ptr(u.t), float(T), _parr(params), len(params), int(ipar),
+                                                          _ptr(v.u.t), float(v.p), _ptr(w.t), _ptr(out.t), C.byref(st),
+                                                          C.byref(sp)), "bk_potrap_fold_border")
+        return BorderedArray(out, st.value), sp.value
+
     def dparam(self, u: HipVec, T: float, params, ipar: int) -> HipVec:
         out = u.similar()
         self.ctx.check(self.ctx.lib.bk_potrap_dparam(self.h, _ptr(u.t), float(T), _parr(params), len(params), int(ipar),
@@ -112,17 +134,25 @@ class PeriodicOrbitTrap:
 
 
 class PoTrapJacobian:
-    """dG(u, T) as an operator handle (bk_potrap_op_create); keeps ``u`` alive."""
+    """dG(u, T) as an operator handle (bk_potrap_op_create), or dG(u, T)^T (``adjoint=True``: bk_potrap_op_adjoint_create); keeps
+    ``u`` alive."""
 
-    def __init__(self, po: PeriodicOrbitTrap, u: HipVec, T: float, params):
+    def __init__(self, po: PeriodicOrbitTrap, u: HipVec, T: float, params, adjoint: bool = False):
         self.po, self.ctx, self.u, self.T, self.params = po, po.ctx, u, float(T), list(params)
+        self.is_adjoint = bool(adjoint)
+        name = "bk_potrap_op_adjoint_create" if self.is_adjoint else "bk_potrap_op_create"
         h = C.c_void_p()
-        self.ctx.check(self.ctx.lib.bk_potrap_op_create(po.h, _ptr(u.t), self.T, _parr(params), len(params), C.byref(h)),
-                       "bk_potrap_op_create")
+        self.ctx.check(getattr(self.ctx.lib, name)(po.h, _ptr(u.t), self.T, _parr(params), len(params), C.byref(h)), name)
         self.h = h
 
     def __call__(self, dx: BorderedArray) -> BorderedArray:
+        if self.is_adjoint:
+            return self.po.jvp_adjoint(self.u, self.T, self.params, dx.u, dx.p)
         return self.po.jvp(self.u, self.T, self.params, dx.u, dx.p)
+
+    def adjoint(self) -> "PoTrapJacobian":
+        """The transposed operator at the same (u, T, params)."""
+        return PoTrapJacobian(self.po, self.u, self.T, self.params, adjoint=not self.is_adjoint)
 
     def __del__(self):
         try:
@@ -134,15 +164,18 @@ class PoTrapJacobian:
 
 class PoTrapPreconditioner:
     """P = diag(A0, 1), A0 the orbit Jacobian with every J_i replaced by Lap (x) I_2 + [[a, -b], [b, a]]; the default
-    a = r, b = nu is the linearisation at the trivial state.  ``set_period`` refuses a Hopf-critical (a, b)."""
+    a = r, b = nu is the linearisation at the trivial state.  ``set_period`` refuses a Hopf-critical (a, b).  ``adjoint=True``:
+    diag(A0^T, 1), the preconditioner of ``PoTrapJacobian.adjoint()`` (bk_precond_potrap_adjoint_create)."""
 
-    def __init__(self, po: PeriodicOrbitTrap, a: float | None = None, b: float | None = None, params=None):
+    def __init__(self, po: PeriodicOrbitTrap, a: float | None = None, b: float | None = None, params=None, adjoint: bool = False):
         self.po, self.ctx = po, po.ctx
         pv = po.prob._pvec(po.prob.params[po.prob.lens]) if params is None else list(params)
         a = pv[0] if a is None else a
         b = pv[2] if b is None else b
         h = C.c_void_p()
-        self.ctx.check(self.ctx.lib.bk_precond_potrap_create(po.h, float(a), float(b), C.byref(h)), "bk_precond_potrap_create")
+        self.is_adjoint = bool(adjoint)
+        name = "bk_precond_potrap_adjoint_create" if self.is_adjoint else "bk_precond_potrap_create"
+        self.ctx.check(getattr(self.ctx.lib, name)(po.h, float(a), float(b), C.byref(h)), name)
         self.h = h
         self.a, self.b = float(a), float(b)
 
@@ -172,7 +205,8 @@ class PoTrapPreconditioner:
 
 def po_solve(J: PoTrapJacobian, pl, rhs: BorderedArray, ls: _GMRES):
     """One GMRES on diag(A0^-1, 1) dG x = diag(A0^-1, 1) rhs (bk_potrap_solve) -> (x, converged, niter).  ``pl``: anything with a
-    preconditioner handle ``.h``; the library refuses one that is not a PoTrapPreconditioner of this orbit's size."""
+    preconditioner handle ``.h``; the library refuses one that is not a PoTrapPreconditioner of this orbit's size.  An adjoint
+    Jacobian goes with an adjoint preconditioner (dG^T and A0^-T); the library refuses a mixed pair."""
     ctx = J.ctx
     x, xt = rhs.u.similar(), C.c_double()
     o = ls._opts()
@@ -180,6 +214,231 @@ def po_solve(J: PoTrapJacobian, pl, rhs: BorderedArray, ls: _GMRES):
     ctx.check(ctx.lib.bk_potrap_solve(ctx.h, J.h, pl.h if pl is not None else None, _ptr(rhs.u.t), float(rhs.p), _ptr(x.t),
                                       C.byref(xt), C.byref(o), C.byref(res)), "bk_potrap_solve")
     return BorderedArray(x, xt.value), bool(res.converged), int(res.niter)
+
+
+def po_bordered_solve(J: PoTrapJacobian, pl, a: BorderedArray, b: BorderedArray, c: float, rhs: BorderedArray, rhs_border: float,
+                      ls: _GMRES):
+    """ONE GMRES on [A a; b' c][x; s] = [rhs; rhs_border], A = dG or dG^T with its T entry, left-preconditioned by diag(A0^-1, 1, 1)
+    (bk_potrap_bordered_solve): regular where dG is singular.  ``a``, ``b``, ``rhs``: BorderedArray(vector, T entry); ``pl`` of the
+    kind of ``J``.  Returns (x, s, converged, niter)."""
+    ctx = J.ctx
+    x, xt, xb = rhs.u.similar(), C.c_double(), C.c_double()
+    o = ls._opts()
+    res = L.SolveResult()
+    ctx.check(ctx.lib.bk_potrap_bordered_solve(ctx.h, J.h, pl.h if pl is not None else None, _ptr(a.u.t), float(a.p), _ptr(b.u.t),
+                                               float(b.p), float(c), _ptr(rhs.u.t), float(rhs.p), float(rhs_border), _ptr(x.t),
+                                               C.byref(xt), C.byref(xb), C.byref(o), C.byref(res)), "bk_potrap_bordered_solve")
+    return BorderedArray(x, xt.value), xb.value, bool(res.converged), int(res.niter)
+
+
+def po_fold_terms(po: PeriodicOrbitTrap, u: HipVec, T: float, params, a: BorderedArray, b: BorderedArray, pl, pl_adjoint, ls: _GMRES):
+    """The bordered vectors of the fold of limit cycles (bk_potrap_fold_terms; MinAugFold.jl:15-69): [dG a; b' 0][v; sigma] = [0; 1]
+    and [dG^T b; a' 0][w; .] = [0; 1], one bordered solve each.  Returns dict(v, w (BorderedArrays), sigma, converged, itlinear)."""
+    ctx = po.ctx
+    v, w = u.similar(), u.similar()
+    vT, wT, sg, cv = C.c_double(), C.c_double(), C.c_double(), C.c_int()
+    it = (C.c_int * 2)()
+    o = ls._opts()
+    ctx.check(ctx.lib.bk_potrap_fold_terms(po.h, _ptr(u.t), float(T), _parr(params), len(params), _ptr(a.u.t), float(a.p),
+                                           _ptr(b.u.t), float(b.p), pl.h, pl_adjoint.h, C.byref(o), _ptr(v.t), C.byref(vT),
+                                           _ptr(w.t), C.byref(wT), C.byref(sg), C.byref(cv), it), "bk_potrap_fold_terms")
+    return dict(v=BorderedArray(v, vT.value), w=BorderedArray(w, wT.value), sigma=sg.value, converged=bool(cv.value),
+                itlinear=(it[0], it[1]))
+
+
+def _fold_preconds(po, ls, params, T, pl, pl_adjoint):
+    if pl is None:
+        pl = _precond_for(po, ls, params).set_period(T)
+    if pl_adjoint is None:
+        pl_adjoint = PoTrapPreconditioner(po, pl.a, pl.b, adjoint=True).set_period(T)
+    return pl, pl_adjoint
+
+
+def newton_fold_po(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params, lens, a: BorderedArray, b: BorderedArray, ls: _GMRES,
+                   tol=1e-10, max_iterations=10, pl=None, pl_adjoint=None):
+    """newton_fold(br_po, indfold; prob = probFold) (cGL2d.jl:347-370) call by call: Newton in the sup norm on
+    G_fold((u, T), p) = (G, sigma) with the section of ``po`` and (a, b) frozen.  Per point bk_potrap_residual and
+    bk_potrap_fold_terms, per step bk_potrap_fold_border, bk_potrap_dparam and ONE bk_potrap_bordered_solve on
+    [dG d_pG; sigma_x' sigma_p][dX; dp] = [G; sigma] (MinAugFold.jl:136-145): every linear system is a bordered one, regular at the
+    fold.  The preconditioners (default a = r, b = nu, period ``T``) stay fixed.  The yardstick and timing baseline of
+    ``newton_fold_po_native``.  Returns dict(u, T, p, residuals, itlinear (per Newton step the GMRES counts of the v solve, the w
+    solve and the step taken from that point), last_terms_its (the v and w counts of the returned point), itlineartot (all of
+    them summed), v, w, sigma, converged, itnewton)."""
+    params = [float(x) for x in params]
+    ipar = po.prob.param_names.index(lens) if isinstance(lens, str) else int(lens)
+    pl, plT = _fold_preconds(po, ls, params, T, pl, pl_adjoint)
+    u, T, pv = orbit.copy(), float(T), list(params)
+
+    def point():
+        G = po.residual(u, T, pv)
+        t = po_fold_terms(po, u, T, pv, a, b, pl, plT, ls)
+        return G, t, max(_norminf(G), abs(t["sigma"]))
+
+    G, t, r = point()
+    res, its = [r], []
+    while len(res) - 1 < max_iterations and res[-1] > tol:
+        sx, sp = po.fold_border(u, T, pv, ipar, t["v"], t["w"].u)
+        dpG = BorderedArray(po.dparam(u, T, pv, ipar), 0.0)
+        dx, dp, _, it = po_bordered_solve(po.jacobian(u, T, pv), pl, dpG, sx, sp, G, t["sigma"], ls)
+        its.append((t["itlinear"][0], t["itlinear"][1], it))
+        u.add_(dx.u, -1.0)
+        T -= dx.p
+        pv[ipar] -= dp
+        G, t, r = point()
+        res.append(r)
+    return dict(u=u, T=T, p=pv[ipar], residuals=res, itlinear=its, v=t["v"], w=t["w"], sigma=t["sigma"], converged=res[-1] < tol,
+                itnewton=len(res) - 1, last_terms_its=t["itlinear"],
+                itlineartot=sum(sum(k) for k in its) + sum(t["itlinear"]))
+
+
+def newton_fold_po_native(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params, lens, a: BorderedArray, b: BorderedArray,
+                          ls: _GMRES, tol=1e-10, max_iterations=10, pl=None, pl_adjoint=None):
+    """``newton_fold_po`` as one library call (bk_potrap_newton_fold); the same results under the same keys."""
+    from .hip import newton_opts
+    params = [float(x) for x in params]
+    ipar = po.prob.param_names.index(lens) if isinstance(lens, str) else int(lens)
+    pl, plT = _fold_preconds(po, ls, params, T, pl, pl_adjoint)
+    ctx = po.ctx
+    u, v, w = orbit.copy(), orbit.similar(), orbit.similar()
+    Tc, pc = C.c_double(float(T)), C.c_double(params[ipar])
+    vT, wT, sg = C.c_double(), C.c_double(), C.c_double()
+    no, o = newton_opts(tol, max_iterations, True), ls._opts()
+    res = L.NewtonResult()
+    its = (C.c_int * (3 * (int(max_iterations) + 1)))()
+    ctx.check(ctx.lib.bk_potrap_newton_fold(po.h, _ptr(u.t), C.byref(Tc), C.byref(pc), _parr(params), len(params), ipar, _ptr(a.u.t),
+                                            float(a.p), _ptr(b.u.t), float(b.p), pl.h, plT.h, C.byref(no), C.byref(o), _ptr(v.t),
+                                            C.byref(vT), _ptr(w.t), C.byref(wT), C.byref(sg), C.byref(res), its),
+              "bk_potrap_newton_fold")
+    k = res.itnewton
+    return dict(u=u, T=Tc.value, p=pc.value, residuals=[res.residuals[i] for i in range(k + 1)],
+                itlinear=[(its[3 * i], its[3 * i + 1], its[3 * i + 2]) for i in range(k)], v=BorderedArray(v, vT.value),
+                w=BorderedArray(w, wT.value), sigma=sg.value, converged=bool(res.converged), itnewton=k, itlineartot=res.itlinear,
+                last_terms_its=(its[3 * k], its[3 * k + 1]))
+
+
+def _norminf_nested(z):
+    """The sup norm of a (nested) BorderedArray; NaN wins."""
+    r = _norminf_nested(z.u) if isinstance(z.u, BorderedArray) else z.u.norminf()
+    t = abs(z.p)
+    return r if (r != r or r > t) else t
+
+
+def _po_fold_classes():
+    """PoFoldProblem and PoFoldLinearSolverMinAug on the surfaces of codim2.py (imported here: codim2 does not know this module)."""
+    from . import codim2 as C2
+
+    class PoFoldProblem(C2._MinAugProblem):
+        """FoldMinimallyAugmentedFormulation + FoldMAProblem with lens2 (MinAugFold.jl; continuation_fold :407-453) on the orbit
+        functional: the ``_MinAugProblem`` surface on states X = BorderedArray(BorderedArray(u, T), p1), parameter p2 = ``lens2``.
+        a, b: BorderedArray(vector, T entry).  The bordered vectors of a point come from bk_potrap_fold_terms (two bordered
+        solves), cached per point; the section of ``po`` and the preconditioners stay as they are handed over."""
+
+        def __init__(self, po: PeriodicOrbitTrap, params, lens1, lens2, a: BorderedArray, b: BorderedArray, ls: _GMRES, pl, pl_adjoint):
+            names = po.prob.param_names
+            self.po, self.prob, self.ctx = po, po.prob, po.ctx
+            self.params = [float(x) for x in params]
+            self.ipar1 = names.index(lens1) if isinstance(lens1, str) else int(lens1)
+            self.ipar2 = names.index(lens2) if isinstance(lens2, str) else int(lens2)
+            if self.ipar1 == self.ipar2:
+                raise ValueError(f"Please choose 2 different parameters. You only passed {lens2}")
+            self.lens1, self.lens2 = names[self.ipar1], names[self.ipar2]
+            self.ls, self.pl, self.pl_adjoint = ls, pl, pl_adjoint
+            self.a, self.b = a, b
+            self.delta = po.prob.delta
+            self.itlinear = 0
+            self._cache = None
+
+        def pvec(self, p1, p2):
+            pv = list(self.params)
+            pv[self.ipar1], pv[self.ipar2] = float(p1), float(p2)
+            return pv
+
+        def terms(self, X, p2: float):
+            """(v, w, sigma) at (X, p2), solved once per point."""
+            c = self._cache
+            if c is not None and c[1] == (X.u.p, X.p, p2) and torch.equal(c[0].t, X.u.u.t):
+                return c[2]
+            t = po_fold_terms(self.po, X.u.u, X.u.p, self.pvec(X.p, p2), self.a, self.b, self.pl, self.pl_adjoint, self.ls)
+            self.itlinear += t["itlinear"][0] + t["itlinear"][1]
+            out = (t["v"], t["w"], t["sigma"])
+            self._cache = (X.u.u.copy(), (X.u.p, X.p, p2), out)
+            return out
+
+        def residual(self, X, p2: float):
+            _, _, sigma = self.terms(X, p2)
+            return BorderedArray(self.po.residual(X.u.u, X.u.p, self.pvec(X.p, p2)), sigma)
+
+        def residual_dparam(self, X, p2: float, eps=None):
+            """dG/dp2 = ((d_p2 G, 0), sigma_p2), analytic."""
+            v, w, _ = self.terms(X, p2)
+            pv = self.pvec(X.p, p2)
+            _, sp2 = self.po.fold_border(X.u.u, X.u.p, pv, self.ipar2, v, w.u)
+            return BorderedArray(BorderedArray(self.po.dparam(X.u.u, X.u.p, pv, self.ipar2), 0.0), sp2)
+
+        def update(self, X, p2: float):
+            """update!(probma, iter, state) (:280-313) after a converged step: a <- w / |w|, b <- v / |v| from the bordered vectors
+            of the new point (T entries included); returns <a, b>."""
+            v, w, _ = self.terms(X, p2)
+            self.a = w.copy().scale_(1.0 / w.norm())
+            self.b = v.copy().scale_(1.0 / v.norm())
+            self._cache = None
+            return self.a.inner(self.b)
+
+    class PoFoldLinearSolverMinAug(C2._MinAugLinearSolver):
+        """FoldLinearSolverMinAug (:168-178) on the orbit functional as bk_potrap_fold_linsolve: the full system
+        [dG d_p1 G; sigma_x' sigma_p1] (:136-145), one bordered solve per right-hand side."""
+
+        def _run(self, J, rhs):
+            P, X = J.ma, J.X
+            v, w, _ = P.terms(X, J.p2)
+            pv = P.pvec(X.p, J.p2)
+            ctx, m = P.ctx, len(rhs)
+            dX = [X.u.u.similar() for _ in rhs]
+            ru = (C.c_void_p * m)(*[r.u.u.t.data_ptr() for r in rhs])
+            dxp = (C.c_void_p * m)(*[d.t.data_ptr() for d in dX])
+            rT = (C.c_double * m)(*[float(r.u.p) for r in rhs])
+            rp = (C.c_double * m)(*[float(r.p) for r in rhs])
+            dT, ds = (C.c_double * m)(), (C.c_double * m)()
+            cv, it = C.c_int(), C.c_int()
+            lo = P.ls._opts()
+            ctx.check(ctx.lib.bk_potrap_fold_linsolve(P.po.h, _ptr(X.u.u.t), float(X.u.p), _parr(pv), len(pv), P.ipar1, _ptr(v.u.t),
+                                                      float(v.p), _ptr(w.u.t), P.pl.h, m, ru, rT, rp, C.byref(lo), dxp, dT, ds,
+                                                      C.byref(cv), C.byref(it)), "bk_potrap_fold_linsolve")
+            return [BorderedArray(BorderedArray(dX[k], dT[k]), ds[k]) for k in range(m)], bool(cv.value), it.value
+
+    return PoFoldProblem, PoFoldLinearSolverMinAug, C2
+
+
+def continuation_fold_po(po: PeriodicOrbitTrap, fold_guess: BorderedArray, p2: float, lens2, a: BorderedArray, b: BorderedArray,
+                         ls: _GMRES, cp: Cn.ContinuationPar, params=None, lens1="r", theta=0.5, update_minaug_every_step=1,
+                         save_sol=False, ds_sequence=None, verbosity=0, pl=None, pl_adjoint=None):
+    """continuation_fold(probFold, br_po, indfold, (@optic _.c5), optcontfold) (cGL2d.jl:381-392; MinAugFold.jl:369-453): PALC on
+    G_fold(X, p2) with X = BorderedArray(BorderedArray(u, T), p1) = ``fold_guess`` through the driver the SH fold and Hopf curves
+    share (codim2._continuation_minaug: Secant tangent, BorderingBLS over PoFoldLinearSolverMinAug, the two starting points by
+    Newton on G_fold).  After every converged step a <- w / |w|, b <- v / |v|.  The section of ``po`` stays frozen; the
+    preconditioners (default a = r, b = nu of ``params``, period of the guess) stay fixed.  ``params``: the full parameter list
+    (default: the problem's).  Returns a codim2._MinAugBranch (p1, p2, ds, itnewton, itlinear -- the GMRES counts of the step,
+    bordered vectors included --, residuals, sol) with T, amplitude and ab = <a, b> per point in addition."""
+    PoFoldProblem, PoFoldLinearSolverMinAug, C2 = _po_fold_classes()
+    params = po.prob._pvec(po.prob.params[po.prob.lens]) if params is None else [float(x) for x in params]
+    pl, plT = _fold_preconds(po, ls, params, fold_guess.u.p, pl, pl_adjoint)
+    P = PoFoldProblem(po, params, lens1, lens2, a, b, ls, pl, plT)
+    br = C2._MinAugBranch()
+    br.T, br.amplitude, br.ab = [], [], []
+
+    def record_x(X, val, tau):
+        br.p1.append(X.p); br.T.append(X.u.p); br.amplitude.append(amplitude(X.u.u)); br.ab.append(val)
+
+    C2._continuation_minaug(P, PoFoldLinearSolverMinAug(), "Fold", br, fold_guess, float(p2), cp, theta, _norminf_nested,
+                            update_minaug_every_step, save_sol, ds_sequence, verbosity, record_x, lambda X: float("nan"),
+                            lambda X: f"p1={X.p:+.8f} T={X.u.p:.6f}")
+    return br
+
+
+def __getattr__(name):
+    if name in ("PoFoldProblem", "PoFoldLinearSolverMinAug"):
+        return dict(zip(("PoFoldProblem", "PoFoldLinearSolverMinAug"), _po_fold_classes()[:2]))[name]
+    raise AttributeError(name)
 
 
 class _PoFunctional:
@@ -277,7 +536,7 @@ def amplitude(u: HipVec) -> float:
 
 def continuation_po_trap(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params, lens, cp: Cn.ContinuationPar, ls: _GMRES,
                          theta=0.5, update_section_every_step=1, verbosity=0, nev=0, detect_bifurcation=0, tol_stability=1e-10,
-                         eig=None):
+                         eig=None, save_sol=False):
     """PALC on the (N M + 1) + 1 system (continuation(poTrapMF, ..., PALC()) of cGL2d.jl:221-260): two Newton solves and the secant
     tangent, then per step newton_palc with BorderingBLS -- two preconditioned solves per Newton step, d_p G analytic --, the
     step-size control of continuation.py and updatesection! after every accepted step (the reference's default).  ``lens``: the
@@ -287,7 +546,9 @@ def continuation_po_trap(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params,
     preconditioner's (a, b), ``eig``), recorded as ``floquet`` (the exponents), ``n_unstable`` (Re sigma > tol_stability), ``n_imag``
     (the unstable ones with |Im sigma| > tol_stability) and ``stable``; ``detect_bifurcation >= 2`` adds ``specialpoints``: one
     dict(step, interval, type, delta, ind_ev) whenever n_unstable changes between two points (``classify_po_bifurcation``; no
-    bisection).  With the defaults nothing of this runs."""
+    bisection).  With the defaults nothing of this runs.  ``save_sol``: every special point also carries ``x`` (a copy of the orbit
+    and T at the point after the crossing, a BorderedArray), ``tau`` (the secant tangent there, BorderedArray(BorderedArray(u, T),
+    p)) and ``param`` -- what ``po_fold_point`` starts from; the records and the library calls are otherwise those of the default."""
     params = [float(x) for x in params]
     ipar = po.prob.param_names.index(lens) if isinstance(lens, str) else int(lens)
     pl = _precond_for(po, ls, params).set_period(T)
@@ -322,7 +583,10 @@ def continuation_po_trap(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params,
         if detect_bifurcation >= 2 and br["n_unstable"] and nu != br["n_unstable"][-1]:
             tp = classify_po_bifurcation(nu, br["n_unstable"][-1], ni, br["n_imag"][-1])
             if tp is not None:
-                br["specialpoints"].append(dict(step=step, interval=(br["p"][-2], br["p"][-1]), **tp))
+                sp = dict(step=step, interval=(br["p"][-2], br["p"][-1]), **tp)
+                if save_sol:
+                    sp.update(x=z.u.copy(), tau=Cn.secant_tangent(z, z_old, ds, theta), param=z.p)
+                br["specialpoints"].append(sp)
         br["floquet"].append(fl["exponents"]); br["n_unstable"].append(nu); br["n_imag"].append(ni); br["stable"].append(nu == 0)
         br["eig_converged"].append(fl["converged"])
 
@@ -357,6 +621,25 @@ def continuation_po_trap(po: PeriodicOrbitTrap, orbit: HipVec, T: float, params,
         z_pred = z.copy().add_(tau, ds)
     br["orbit"] = z.u
     return br
+
+
+def po_fold_point(br: dict, ind: int = 0, po: PeriodicOrbitTrap | None = None, params=None, lens=None):
+    """The guess of newton_fold(br_po, indfold) from special point ``ind`` of a ``continuation_po_trap(..., save_sol=True)`` branch
+    (fold_point, cGL2d.jl:354; newton_fold :244-247): dict(orbit, T, p, a, b) with a = b = the (u, T) part of the saved tangent,
+    normalised in the 2-norm.  With ``po``, ``params`` and ``lens`` also updatesection! at the guess (cGL2d.jl:365), the section
+    the fold system then keeps frozen."""
+    sp = br["specialpoints"][ind]
+    if "x" not in sp:
+        raise ValueError("po_fold_point needs a branch of continuation_po_trap(..., save_sol=True)")
+    x, tau = sp["x"], sp["tau"].u.copy()
+    nrm = math.sqrt(tau.u.norm() ** 2 + tau.p ** 2)
+    tau.u.scale_(1.0 / nrm)
+    tau.p /= nrm
+    if po is not None:
+        pv = [float(v) for v in params]
+        pv[po.prob.param_names.index(lens) if isinstance(lens, str) else int(lens)] = float(sp["param"])
+        po.update_section(x.u, x.p, pv)
+    return dict(orbit=x.u.copy(), T=float(x.p), p=float(sp["param"]), a=tau, b=tau)
 
 
 def get_periodic_orbit(po: PeriodicOrbitTrap, u: HipVec, T: float):

@@ -980,6 +980,66 @@ int bk_precond_potrap_transform_paths(bk_precond* pl, int paths[2]);
 int bk_potrap_solve(bk_ctx* ctx, bk_op* op, bk_precond* pl, const double* rhs, double rhs_tail, double* x, double* x_tail,
                     const bk_gmres_opts* opts, bk_solve_result* result);
 
+/* ------------------------------------------------------------------ the adjoint of the orbit Jacobian (pofold.hip) --
+ * dG(u, T)^T on (w, tau), what the left null vector of the fold of limit cycles is computed with (src/codim2/MinAugFold.jl:15-69
+ * on the Trapeze functional, cGL2d.jl:347-392).  With next(j) = j + 1, next(K - 1) = 0, s_j = w_j + w_next(j), q_j = J_j^T s_j:
+ *     out_j = (w_j - w_next(j)) - (h / 2) q_j - [j = 0] w_K + tau phi_j (j < K),   out_K = w_K + tau phi_K,
+ *     *out_tail = -(1 / (2 M)) sum_{j < K} <F(u_j), s_j>.
+ * One marching pass, one adjoint stencil evaluation per slice; option "potrap_chunks" as for bk_potrap_residual, out has the same
+ * bits for every chunk count.  out must not alias u, w or the section.                                                       */
+int bk_potrap_jvp_adjoint(bk_potrap* h, const double* u, double T, const double* params, int nparams, const double* w, double tau,
+                          double* out, double* out_tail);
+/* dG(u, T)^T as an operator handle with one host tail scalar: REFERENCES u.                                                  */
+int bk_potrap_op_adjoint_create(bk_potrap* h, const double* u, double T, const double* params, int nparams, bk_op** out);
+/* diag(A0^T, 1): the DST-I is symmetric and L0^T multiplies a sine mode by conj(mu_k), so per mode w_K = f_K, f_0 <- f_0 + f_K and
+ * the cyclic recurrence runs backwards in time, w_j = conj(rho) w_next(j) + f_j / conj(alpha).  bk_precond_potrap_set_period (the
+ * same guards: the moduli are equal), bk_precond_apply, bk_precond_potrap_transform_paths and bk_precond_destroy work on it.
+ * bk_potrap_solve takes the adjoint operator with the adjoint preconditioner and refuses a mixed pair.                        */
+int bk_precond_potrap_adjoint_create(bk_potrap* h, double a, double b, bk_precond** out);
+/* ONE GMRES on the doubly bordered system
+ *     [A a; b' c][x; x_border] = [rhs; rhs_border],    A = dG or dG^T with its T entry (op of either kind, pl of the same kind),
+ * left-preconditioned by diag(A0^-1, 1, 1) (A0^-T for the adjoint): regular where dG is singular, i.e. at a fold of limit
+ * cycles.  a, b, rhs, x: M N doubles on the device, each with a host T entry (*_tail); c, rhs_border, *x_border the border
+ * scalars.  A0^-1 a is formed once per solve; per application the column update and the row dot are one pass.  x must not alias
+ * rhs, a or b.                                                                                                               */
+int bk_potrap_bordered_solve(bk_ctx* ctx, bk_op* op, bk_precond* pl, const double* a, double a_tail, const double* b, double b_tail,
+                             double c, const double* rhs, double rhs_tail, double rhs_border, double* x, double* x_tail,
+                             double* x_border, const bk_gmres_opts* opts, bk_solve_result* result);
+/* The border row of the Jacobian of the fold system of the orbit functional (MinAugFold.jl:90-97, :131, :136-145) for params[ipar]
+ * from the bordered vectors v (with its T entry v_T) and w, in ONE pass over u, v, w:
+ *     <(sigx, *sigx_T), X> = -<w, d2G(u, T)[v, X]> for every X,      *sigma_p = -<w, d_p(dG) v>,
+ * with the section frozen.  Through s_j = w_j + w_next(j), q_j = J_j^T s_j: sigx_j = (h / 2) (B_j[v_j, .])^T s_j + (v_T / (2 M)) q_j,
+ * sigx_K = 0, sigx_T = (1 / (2 M)) sum <q_j, v_j>, sigma_p = sum <s_j, (h / 2) D_p(u_j) v_j + (v_T / (2 M)) d_pF(u_j)>.
+ * sigx must not alias u, v or w.                                                                                             */
+int bk_potrap_fold_border(bk_potrap* h, const double* u, double T, const double* params, int nparams, int ipar, const double* v,
+                          double v_T, const double* w, double* sigx, double* sigx_T, double* sigma_p);
+/* The bordered vectors of the fold of limit cycles (MinAugFold.jl:15-69 on the Trapeze functional) at (u, T, params):
+ *     [dG a; b' 0][v; sigma] = [0; 1],      [dG^T b; a' 0][w; sigma2] = [0; 1],
+ * one bk_potrap_bordered_solve each (pl forward, pl_adjoint of bk_precond_potrap_adjoint_create, periods set).  a, b, v, w carry
+ * a T entry.  itlinear[0] / [1]: the GMRES counts of the v / w solve.                                                         */
+int bk_potrap_fold_terms(bk_potrap* h, const double* u, double T, const double* params, int nparams, const double* a, double a_T,
+                         const double* b, double b_T, bk_precond* pl, bk_precond* pl_adjoint, const bk_gmres_opts* opts, double* v,
+                         double* v_T, double* w, double* w_T, double* sigma, int* converged, int itlinear[2]);
+/* The linear solver of the fold system of the orbit functional (FoldLinearSolverMinAug, MinAugFold.jl:136-145, :168-178) at
+ * (u, T, params) with the bordered vectors v (T entry v_T) and w of that point, for nrhs = 1 or 2 right-hand sides (rhsu[k] device,
+ * rhsT[k] and rhsp[k] host: the T entry and the sigma row):  [dG d_pG; sigx' sigma_p][dX_k; dsigma_k] = [rhs_k; rhsp_k] with the
+ * border of bk_potrap_fold_border for params[ipar], ONE bk_potrap_bordered_solve per right-hand side (pl forward, period set).
+ * dX[k] device, dXT[k] and dsigma[k] host; *itlinear = the GMRES counts summed.  dX must not alias a right-hand side, u, v or w. */
+int bk_potrap_fold_linsolve(bk_potrap* h, const double* u, double T, const double* params, int nparams, int ipar, const double* v,
+                            double v_T, const double* w, bk_precond* pl, int nrhs, const double* const* rhsu, const double* rhsT,
+                            const double* rhsp, const bk_gmres_opts* opts, double* const* dX, double* dXT, double* dsigma,
+                            int* converged, int* itlinear);
+/* newton_fold on the orbit functional (cGL2d.jl:347-370; MinAugFold.jl:211-233) under the semantics of _newton: (u, *T, *p) =
+ * guess on entry, the fold of limit cycles on exit; params[ipar] is the fold parameter; the section of h and (a, b) stay frozen.
+ * Per point the two solves of bk_potrap_fold_terms, per step [dG d_pG; sigx' sigma_p][dX; dp] = [G; sigma] as one
+ * bk_potrap_bordered_solve (the branch :136-145).  tol applies to max(|G|_inf, |G_T|, |sigma|) (norm_inf) or the 2-norm.  On exit
+ * v, w, *sigma are those of the returned point.  itlinear_steps (may be NULL; 3 (max_iterations + 1) ints): per point the
+ * counts of the v and w solves, then of the step taken from it.                                                              */
+int bk_potrap_newton_fold(bk_potrap* h, double* u, double* T, double* p, const double* params, int nparams, int ipar, const double* a,
+                          double a_T, const double* b, double b_T, bk_precond* pl, bk_precond* pl_adjoint, const bk_newton_opts* no,
+                          const bk_gmres_opts* opts, double* v, double* v_T, double* w, double* w_T, double* sigma,
+                          bk_newton_result* res, int* itlinear_steps);
+
 /* ------------------------------------------------------------------ Floquet multipliers of trapezoid orbits --------
  * The matrix-free monodromy of FloquetQaD (src/periodicorbit/Floquet.jl:48-85), MonodromyQaD_matrix_free(::Trapeze, ...)
  * (:285-315): K = M - 1 sequential steps x <- (I - hh J_i)^-1 (I + hh J_prev(i)) x, hh = T (1 / M) / 2.  Here the same vector is
