@@ -210,6 +210,9 @@ SIGNATURES = {
     "bk_newton_palc": (I, [VP, VP, VP, c_double_p, VP, D, VP, D, D, D, c_double_p, I, I, D, D,
                            C.POINTER(NewtonOpts), C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP,
                            C.POINTER(NewtonResult)]),
+    "bk_newton_palc_from": (I, [VP, VP, VP, VP, c_double_p, VP, D, VP, D, D, D, c_double_p, I, I, D, D,
+                                C.POINTER(NewtonOpts), C.POINTER(BorderingOpts), C.POINTER(GmresOpts), VP,
+                                C.POINTER(NewtonResult)]),
     "bk_d2f": (I, [VP, VP, c_double_p, I, VP, VP, VP]),
     "bk_djdp": (I, [VP, VP, c_double_p, I, I, VP, VP]),
     "bk_fold_contract": (I, [VP, VP, c_double_p, I, I, VP, VP, I, C.POINTER(VP), c_double_p]),

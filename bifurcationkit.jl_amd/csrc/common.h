@@ -22,7 +22,8 @@ constexpr int kMaxBasis = 64;      // largest Krylov dimension + 1 the fused ker
 constexpr int kRedSlots = 256;     // doubles in the reduction result buffers
 constexpr int kRedBlocks = 1024;   // blocks of a reduction kernel (stage 1); stage 2 is one block
 // values per workgroup the stage-1 kernels may leave in d_partials: multidot kMaxBasis + 2, the Gram variant 2 * 32 + 1, block_dots
-// 4 * 8 + 36 = 68 (vecops.hip: static_asserts at the launch sites); every launcher checks grid * values against kPartialDoubles
+// 4 * 8 + 36 = 68 and 8 * 6 + 21 = 69 (vecops.hip, block_dots_wide.hip: static_asserts at the launch sites); every launcher checks
+// grid * values against kPartialDoubles
 constexpr int kPartialVals = 72;
 constexpr size_t kPartialDoubles = (size_t)kRedBlocks * kPartialVals;
 constexpr double kCancelTol = 1e-8;   // Pythagorean norm b^2 = |w|^2 - |h|^2 is trusted while b^2 > kCancelTol |w|^2 (host and device Arnoldi steps)
@@ -244,6 +245,11 @@ int v_multiaxpy(bk_ctx* ctx, size_t n, const double* V, size_t ldv, int k, const
 bool v_block_ok(bk_ctx* ctx, size_t n, const double* V, size_t ldv);
 int v_block_dots(bk_ctx* ctx, size_t n, const double* V, size_t ldv, int kold, int r0, int nr, double* D, double* T);
 int v_block_axpy(bk_ctx* ctx, size_t n, double* V, size_t ldv, int k, int s, const double* Cm, const double* Tm);
+// block_dots_wide.hip: the first launch of v_block_dots for 5 < nr <= kBlockDotsWideNr right-hand vectors and kold > 4 (option
+// block_dots_wide) -- min(kold, 8) basis vectors, the right-hand vectors (Rv = their first slot) and the triangle in ONE launch
+constexpr int kBlockDotsWideNr = 6;
+int block_dots_wide(bk_ctx* ctx, int grid, bool nt, size_t n, const double* V, size_t ldv, int kold, const double* Rv, int nr,
+                    double* D, double* T, int* done);
 // device-resident orthogonalisation step (vecops.hip): rec / coef are device buffers of kMaxBasis + 2 doubles
 // gram != NULL: the Gram-corrected single-pass step (device Gram matrix, (kMaxBasis + 1)^2 doubles, owned by the caller)
 int v_arnoldi_step_dev(bk_ctx* ctx, size_t n, double* V, size_t ldv, int k, const double* w, double eta, double orth_tol,

@@ -224,7 +224,6 @@ int bk_cont_step(bk_cont* c, bk_cont_step_result* r) {
         return 0;
     }
     double* x = c->work;
-    BK_TRY(v_copy(ctx, c->n, c->predu, x));
     double p = c->predp;
     bk_newton_result nr = {};
     if (c->predp <= c->co.p_min || c->predp >= c->co.p_max) {
@@ -234,12 +233,14 @@ int bk_cont_step(bk_cont* c, bk_cont_step_result* r) {
         double par[BK_MAX_PARAMS];
         for (int i = 0; i < c->nparams; ++i) par[i] = c->params[i];
         par[c->ipar] = p;
+        BK_TRY(v_copy(ctx, c->n, c->predu, x));
         BK_TRY(bk_newton(ctx, c->prob, x, par, c->nparams, &c->no, &c->lo, c->pl, &nr));
         r->natural = 1;
     } else {
-        // corrector!: newton_palc from the predictor; z (the last point) and tau are inputs
-        BK_TRY(bk_newton_palc(ctx, c->prob, x, &p, c->zu, c->zp, c->tauu, c->taup, c->ds, c->co.theta, c->params,
-                              c->nparams, c->ipar, c->co.p_min, c->co.p_max, &c->no, &c->bo, &c->lo, c->pl, &nr));
+        // corrector!: newton_palc from the predictor, which is only read (no copy of it where the first update can write x); z (the
+        // last point) and tau are inputs
+        BK_TRY(bk_newton_palc_from(ctx, c->prob, c->predu, x, &p, c->zu, c->zp, c->tauu, c->taup, c->ds, c->co.theta, c->params,
+                                   c->nparams, c->ipar, c->co.p_min, c->co.p_max, &c->no, &c->bo, &c->lo, c->pl, &nr));
     }
     r->converged = nr.converged; r->itnewton = nr.itnewton; r->itlinear = nr.itlinear;
     c->converged = nr.converged != 0;

@@ -302,11 +302,12 @@ int linsolve(bk_ctx* ctx, bk_op* J, const double* rhs, double* x, double a0, dou
 int linsolve2(bk_ctx* ctx, bk_op* J, const double* rhs1, double* x1, const double* rhs2, double* x2, double a0, double a1,
               const bk_gmres_opts& o, bk_precond* pl, GmresResult* r1, GmresResult* r2);
 // BorderingBLS (src/LinearBorderSolver.jl:88-166) on an unbordered operator (solver.hip; bk_bls_bordering without the checks)
-// xnew (optional, check_precision off only): also xnew <- xnew - dX in the tail pass; dX then holds x1 without the dl term
+// xnew (optional, check_precision off only): also xnew <- xsrc - dX in the tail pass (xsrc = NULL: xnew itself; otherwise a vector
+// that does not overlap xnew and is left as it is); dX then holds x1 without the dl term
 int bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R, double nn,
                   double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_bordering_opts& bo,
                   const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2],
-                  double* xnew = nullptr);
+                  double* xnew = nullptr, const double* xsrc = nullptr);
 // The operator of a left-preconditioned solve for operators built on top of it (solver.hip: ShiftPrecOp behind prec_op_create;
 // delete `op` after the solve).  The solve is about alpha0 I + alpha1 op: (0, 1) on the literal chain, the solve's
 // (t_alpha0, t_alpha1) in stencil-free mode (tmode), where op applies T.

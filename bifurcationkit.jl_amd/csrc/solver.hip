@@ -1402,11 +1402,13 @@ namespace {
 // The bordered tail and the Newton update as ONE pass (option palc_fuse_update): t = a dx + x1, then x = x - t, element by element
 // what the two v_axpby calls  x1 <- a dx + 1 x1  and  x <- -1 x1 + 1 x  compute (their products by +-1 are exact) -- the product and
 // the two sums rounded on their own, a zero a skips the dx term as v_axpbyz skips an operand (0.0 + x1) -- without the store and the
-// reload of x1: three read streams and one write instead of 2 x (2 + 1).  x is read and written in place (no __restrict__ on it); dx
-// and x1 are only read and must not alias x.
+// reload of x1: three read streams and one write instead of 2 x (2 + 1).  The third operand is read from xs and the result written
+// to x: xs == x is the update in place, xs != x (the corrector's first iteration, bk_newton_palc_from) leaves the predictor as it
+// is and saves the copy of it (no __restrict__ on either); every lane reads its elements of xs before it writes them to x.  dx and
+// x1 are only read and must not alias x.
 template <int VEC, bool NTH>
 __global__ void __launch_bounds__(kThreads) palc_update_kernel(size_t n, double a, const double* __restrict__ dx,
-                                                               const double* __restrict__ x1, double* x, int has_dx) {
+                                                               const double* __restrict__ x1, const double* xs, double* x, int has_dx) {
     auto one = [&](double d, double v, double xv) {
         double t = 0.0;
         if (has_dx) t = __dmul_rn(a, d);
@@ -1421,7 +1423,7 @@ __global__ void __launch_bounds__(kThreads) palc_update_kernel(size_t n, double 
             for (int u = 0; u < UU; ++u) {
                 dv[u] = ld2<NTH>(dx, i0 + u * st);
                 vv[u] = ld2<NTH>(x1, i0 + u * st);
-                xv[u] = ld2<NTH>(x, i0 + u * st);
+                xv[u] = ld2<NTH>(xs, i0 + u * st);
             }
 #pragma unroll
             for (int u = 0; u < UU; ++u) {
@@ -1434,38 +1436,40 @@ __global__ void __launch_bounds__(kThreads) palc_update_kernel(size_t n, double 
                 }
             }
         });
-        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = one(dx[n - 1], x1[n - 1], x[n - 1]);
+        if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) x[n - 1] = one(dx[n - 1], x1[n - 1], xs[n - 1]);
     } else {
-        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) x[i] = one(dx[i], x1[i], x[i]);
+        for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads) x[i] = one(dx[i], x1[i], xs[i]);
     }
 }
 
 }  // namespace
 
-// x <- x - (x1 - dl dx): the launches v_axpby(-dl, dx, 1, x1) and v_axpby(-1, x1, 1, x) as one (x1 is left as it is)
-int palc_update(bk_ctx* ctx, size_t n, double dl, const double* dx, const double* x1, double* x) {
+// x <- xs - (x1 - dl dx), xs == x or a vector that does not overlap x: the launches v_axpby(-dl, dx, 1, x1) and v_axpby(-1, x1, 1, x)
+// as one (x1 is left as it is)
+int palc_update(bk_ctx* ctx, size_t n, double dl, const double* dx, const double* x1, const double* xs, double* x) {
     if (n == 0) return 0;
     ProfScope ps(ctx, "blas1", 32.0 * n);
-    const bool vec = aligned16(dx) && aligned16(x1) && aligned16(x);
+    const bool vec = aligned16(dx) && aligned16(x1) && aligned16(xs) && aligned16(x);
     const int grid = grid_for(n, vec ? 2 : 1, 4096);
     const double a = -dl;
     const int has_dx = a != 0.0 ? 1 : 0;
     if (vec && nt_hint(ctx, n))
-        hipLaunchKernelGGL((palc_update_kernel<2, true>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, x, has_dx);
+        hipLaunchKernelGGL((palc_update_kernel<2, true>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, xs, x, has_dx);
     else if (vec)
-        hipLaunchKernelGGL((palc_update_kernel<2, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, x, has_dx);
+        hipLaunchKernelGGL((palc_update_kernel<2, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, xs, x, has_dx);
     else
-        hipLaunchKernelGGL((palc_update_kernel<1, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, x, has_dx);
+        hipLaunchKernelGGL((palc_update_kernel<1, false>), dim3(grid), dim3(kThreads), 0, ctx->stream, n, a, dx, x1, xs, x, has_dx);
     BK_HIP(ctx, hipGetLastError());
     return 0;
 }
 
 // BEC, src/LinearBorderSolver.jl:125-144.  x1 <- (shift+J)^-1 R - dl * dx.
-// xnew != NULL (bk_newton_palc, option palc_fuse_update): the tail pass is palc_update, xnew <- xnew - (x1 - dl dx), and x1 is left
-// holding (shift+J)^-1 R WITHOUT the dl term -- only for callers that do not read x1 afterwards.
+// xnew != NULL (bk_newton_palc, option palc_fuse_update): the tail pass is palc_update, xnew <- xsrc - (x1 - dl dx) (xsrc = NULL:
+// xnew itself), and x1 is left holding (shift+J)^-1 R WITHOUT the dl term -- only for callers that do not read x1 afterwards.
 static int bec(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R, double nn,
                double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_gmres_opts& ls,
-               bk_precond* pl, BorderingState& st, double* x1, double* dl, int* cv, int it[2], double* xnew = nullptr) {
+               bk_precond* pl, BorderingState& st, double* x1, double* dl, int* cv, int it[2], double* xnew = nullptr,
+               const double* xsrc = nullptr) {
     const size_t n = J->n;
     GmresResult r1;
     const double a0 = has_shift ? shift : 0.0;
@@ -1480,7 +1484,7 @@ static int bec(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, doubl
     BK_TRY(v_dot2(ctx, n, dzu, x1, st.dx, d));
     d[0] *= dotscale; d[1] *= dotscale;
     *dl = (nn - d[0] * xiu) / (dzp * xip - d[1] * xiu);
-    if (xnew) BK_TRY(palc_update(ctx, n, *dl, st.dx, x1, xnew));
+    if (xnew) BK_TRY(palc_update(ctx, n, *dl, st.dx, x1, xsrc ? xsrc : xnew, xnew));
     else BK_TRY(v_axpby(ctx, n, -(*dl), st.dx, 1.0, x1));
     *cv = r1.converged & st.cv_dx;
     it[0] = r1.niter; it[1] = st.it_dx;
@@ -1490,16 +1494,16 @@ static int bec(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, doubl
 int bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R, double nn,
                   double xiu, double xip, bool has_shift, double shift, double dotscale, const bk_bordering_opts& bo,
                   const bk_gmres_opts& ls, bk_precond* pl, double* dX, double* dl, int* converged, int itlinear[2],
-                  double* xnew) {
-    // xnew (optional; needs check_precision off): the Newton update xnew <- xnew - dX rides in the tail pass of the one BEC pass, and
-    // dX is left holding x1 = (shift+J)^-1 R without the dl term (see bec)
+                  double* xnew, const double* xsrc) {
+    // xnew (optional; needs check_precision off): the Newton update xnew <- xsrc - dX (xsrc = NULL: xnew) rides in the tail pass of
+    // the one BEC pass, and dX is left holding x1 = (shift+J)^-1 R without the dl term (see bec)
     if (xnew && bo.check_precision) return set_error(ctx, "bls_bordering: the fused update needs check_precision off");
     const size_t n = J->n;
     WsGuard ws(ctx);
     BorderingState st;
     BK_TRY(ws.get(n, &st.dx));
     int cv = 0, it[2] = {0, 0};
-    BK_TRY(bec(ctx, J, dR, dzu, dzp, R, nn, xiu, xip, has_shift, shift, dotscale, ls, pl, st, dX, dl, &cv, it, xnew));
+    BK_TRY(bec(ctx, J, dR, dzu, dzp, R, nn, xiu, xip, has_shift, shift, dotscale, ls, pl, st, dX, dl, &cv, it, xnew, xsrc));
     int k = 0;
     bool fail = true;
     double *dXr = nullptr, *dX1 = nullptr;
@@ -1589,7 +1593,7 @@ int bk_bls_bordering(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu,
 int bk_palc_update(bk_ctx* ctx, size_t n, double dl, const double* dx, const double* x1, double* x) {
     if (!ctx || !dx || !x1 || !x) return -1;
     if (x == dx || x == x1) return set_error(ctx, "bk_palc_update: x must not alias dx or x1");
-    return palc_update(ctx, n, dl, dx, x1, x);
+    return palc_update(ctx, n, dl, dx, x1, x, x);
 }
 
 int bk_bls_matrixfree(bk_ctx* ctx, bk_op* J, const double* dR, const double* dzu, double dzp, const double* R,
@@ -1699,6 +1703,15 @@ int newton_cb(const bk_newton_opts* no, const double* x, const double* fx, doubl
     return 1;
 }
 
+// x <- x0 for a corrector that has to run in place, or whose loop never ran.  Accounted under a profiling scope of its own: whether a
+// corrector call copied its predictor is read off "entry_copy", and "blas1" keeps counting the passes of the iterations alone.
+static int palc_entry_copy(bk_ctx* ctx, size_t n, const double* x0, double* x) {
+    if (n == 0) return 0;
+    ProfScope ps(ctx, "entry_copy", 16.0 * n);
+    BK_HIP(ctx, hipMemcpyAsync(x, x0, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    return 0;
+}
+
 }  // namespace bk
 
 extern "C" {
@@ -1743,7 +1756,19 @@ int bk_newton_palc(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
                    const double* tauu, double taup, double ds, double theta, const double* params, int nparams,
                    int ipar, double p_min, double p_max, const bk_newton_opts* no, const bk_bordering_opts* bo,
                    const bk_gmres_opts* lsopts, bk_precond* pl, bk_newton_result* res) {
-    if (!ctx || !prob || !x || !p || !z0u || !tauu || !params || !no || !bo || !lsopts || !res) return -1;
+    return bk_newton_palc_from(ctx, prob, x, x, p, z0u, z0p, tauu, taup, ds, theta, params, nparams, ipar, p_min, p_max, no, bo,
+                               lsopts, pl, res);
+}
+
+// The corrector from a predictor x0 that stays as it is (x0 == x: in place, bk_newton_palc).  Where the Newton update rides in the
+// bordering solve's tail pass (fuse_update below) the first iteration reads x0 -- entry residual, arc-length equation, dF/dp, the
+// Jacobian handle, both solves -- and its update writes x = x0 - u; the later iterations run in place on x.  No copy of x0 then
+// (option palc_entry_copy = 1 makes it first, as every other path does: line search, check_precision, MatrixFreeBLS).
+int bk_newton_palc_from(bk_ctx* ctx, bk_problem* prob, const double* x0, double* x, double* p, const double* z0u, double z0p,
+                        const double* tauu, double taup, double ds, double theta, const double* params, int nparams,
+                        int ipar, double p_min, double p_max, const bk_newton_opts* no, const bk_bordering_opts* bo,
+                        const bk_gmres_opts* lsopts, bk_precond* pl, bk_newton_result* res) {
+    if (!ctx || !prob || !x0 || !x || !p || !z0u || !tauu || !params || !no || !bo || !lsopts || !res) return -1;
     if (ipar < 0 || ipar >= nparams || nparams > BK_MAX_PARAMS) return set_error(ctx, "bad parameter index");
     if (no->max_iterations > BK_MAX_NEWTON_ITER) return set_error(ctx, "max_iterations > %d", BK_MAX_NEWTON_ITER);
     const size_t n = prob->nloc;
@@ -1774,25 +1799,31 @@ int bk_newton_palc(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
         *out = (d * dotscale * theta + (pp - z0p) * taup * (1.0 - theta) - ds) - (dz0 * dotscale * theta);
         return 0;
     };
+    // option palc_fuse_update (read once per corrector call): BorderingBLS without check_precision and no line search -- nobody reads
+    // u after the update, so x <- x - u rides in the tail pass of the bordering solve (bls_bordering: xnew)
+    const bool fuse_update = bo->kind == 0 && bo->check_precision == 0 && !linesearch && ctx->opt("palc_fuse_update", 1.0) != 0.0;
+    // cur = the current iterate: the predictor x0 itself until the first fused update has written x
+    const double* cur = x;
+    if (x0 != x) {
+        if (fuse_update && ctx->opt("palc_entry_copy", 0.0) == 0.0) cur = x0;
+        else BK_TRY(palc_entry_copy(ctx, n, x0, x));
+    }
     double pc = *p;
     par[ipar] = pc;
-    BK_TRY(bk_residual(prob, x, par, nparams, res_f));
+    BK_TRY(bk_residual(prob, cur, par, nparams, res_f));
     double res_n, rf;
-    BK_TRY(Nfun(x, pc, &res_n));
+    BK_TRY(Nfun(cur, pc, &res_n));
     BK_TRY(norm_of(ctx, n, res_f, inf, &rf));
     double r = std::max(rf, std::fabs(res_n));
     int step = 0, itlin = 0;
     res->residuals[0] = r;
     bool line_step = true;
-    // option palc_fuse_update (read once per corrector call): BorderingBLS without check_precision and no line search -- nobody reads
-    // u after the update, so x <- x - u rides in the tail pass of the bordering solve (bls_bordering: xnew)
-    const bool fuse_update = bo->kind == 0 && bo->check_precision == 0 && !linesearch && ctx->opt("palc_fuse_update", 1.0) != 0.0;
-    int compute = newton_cb(no, x, res_f, r, 0, 0, pc, z0u, z0p, 0);                // Palc.jl:235
+    int compute = newton_cb(no, cur, res_f, r, 0, 0, pc, z0u, z0p, 0);              // Palc.jl:235
     while (step < no->max_iterations && r > no->tol && line_step && compute) {
         par[ipar] = pc;                                    // dFdp = (F(x, p + eps) - res_f)/eps, Palc.jl:239-240
-        BK_TRY(prob->dparam(x, par, nparams, ipar, eps, res_f, dFdp));
+        BK_TRY(prob->dparam(cur, par, nparams, ipar, eps, res_f, dFdp));
         bk_op* J = nullptr;
-        BK_TRY(bk_jacobian(prob, x, par, nparams, &J));
+        BK_TRY(bk_jacobian(prob, cur, par, nparams, &J));
         double up = 0.0;
         int cv = 0, it[2] = {0, 0};
         int s;
@@ -1802,10 +1833,11 @@ int bk_newton_palc(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
             it[0] = itm; it[1] = 0;
         } else {
             s = bls_bordering(ctx, J, dFdp, tauu, taup, res_f, res_n, theta, 1.0 - theta, false, 0.0, dotscale, *bo,
-                              *lsopts, pl, u, &up, &cv, it, fuse_update ? x : nullptr);
+                              *lsopts, pl, u, &up, &cv, it, fuse_update ? x : nullptr, cur);
         }
         bk_op_destroy(J);
         if (s != 0) return s;
+        cur = x;                                             // (cur != x only with fuse_update: the tail pass has written x = x0 - u)
         itlin += it[0] + it[1];
         if (linesearch) {                                    // Palc.jl:254-281
             line_step = false;
@@ -1841,6 +1873,7 @@ int bk_newton_palc(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
         res->residuals[step] = r;
         compute = newton_cb(no, x, res_f, r, step, it[0] + it[1], pc, z0u, z0p, 0);   // Palc.jl:294
     }
+    if (cur != x) BK_TRY(palc_entry_copy(ctx, n, x0, x));  // no iteration ran: the result is the predictor
     *p = pc;
     res->converged = (res->residuals[step] < no->tol) & newton_cb(no, x, res_f, r, step, 0, pc, z0u, z0p, 0);   // :297
     res->itnewton = step;

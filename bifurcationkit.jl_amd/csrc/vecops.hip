@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "block_dots_body.h"
 #include "common.h"
 #include "sstep.h"
 #include "stream.h"
@@ -311,11 +312,34 @@ __global__ void __launch_bounds__(kThreads) minres_update_kernel(size_t n, doubl
     }
 }
 
+// max |x_i| over n2 16-byte items, four of them in flight per lane (a maximum does not depend on the order of its operands)
+template <bool NTH>
+__device__ __forceinline__ double absmax_items(const double* __restrict__ xa, size_t n2) {
+    double m = 0.0;
+    stream_loop<4>(n2, [&](auto uc, size_t i0, size_t st) {
+        constexpr int UU = decltype(uc)::value;
+        double2 v[UU];
+#pragma unroll
+        for (int u = 0; u < UU; ++u) v[u] = ld2<NTH>(xa, i0 + u * st);
+#pragma unroll
+        for (int u = 0; u < UU; ++u) { m = max_nan(m, fabs(v[u].x)); m = max_nan(m, fabs(v[u].y)); }
+    });
+    return m;
+}
+
+// The 16-byte walk starts at the first 16-byte boundary of x: a vector that is only 8-byte aligned gives up its first element, an
+// odd remainder its last one, both to lane 0 of workgroup 0.  Non-temporal loads from 2^22 elements on (the length at which
+// nt_hint sends the other streaming kernels there; this kernel's argument list has no room for the option).
 __global__ void __launch_bounds__(kThreads) absmax_kernel(size_t n, const double* __restrict__ x,
                                                           double* __restrict__ partials) {
-    const size_t stride = (size_t)gridDim.x * kThreads;
-    double m = 0.0;
-    for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += stride) m = max_nan(m, fabs(x[i]));
+    const size_t head = (n > 0 && ((uintptr_t)x & 15) != 0) ? 1 : 0;
+    const double* xa = x + head;
+    const size_t rest = n - head;
+    double m = n >= ((size_t)1 << 22) ? absmax_items<true>(xa, rest >> 1) : absmax_items<false>(xa, rest >> 1);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (head) m = max_nan(m, fabs(x[0]));
+        if (rest & 1) m = max_nan(m, fabs(x[n - 1]));
+    }
     __shared__ double sm[4];
     m = wave_max(m);
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
@@ -634,93 +658,12 @@ __global__ void __launch_bounds__(kThreads) multiaxpy_c_kernel(size_t n, const d
 // values (sstep::tri order).  Unused right-hand slots (r >= nr) are never loaded and contribute exact zeros.
 // NRT = right-hand slots of this instantiation (8, or 5 for the usual LAST block of a solve -- one step plus the previous block's four
 // unmeasured vectors -- which then fits 8 basis vectors AND the triangle into one launch: 55 accumulators); per workgroup KB x NRT
-// values [i * NRT + r], then the NRT (NRT + 1) / 2 triangle values in row order.
+// values [i * NRT + r], then the NRT (NRT + 1) / 2 triangle values in row order.  The body is block_dots_body.h, shared with the
+// 6-slot launch of block_dots_wide.hip.
 template <int KB, bool TRI, int U, bool LDNT, int NRT = sstep::kR>
 __global__ void __launch_bounds__(kThreads) block_dots_kernel(size_t n, const double* __restrict__ V, size_t ldv, int kb,
                                                               const double* __restrict__ Rv, int nr, double* __restrict__ partials) {
-    constexpr int NR = NRT, NT3 = TRI ? NRT * (NRT + 1) / 2 : 1;
-    double acc[KB > 0 ? KB : 1][NR], tri[NT3];
-#pragma unroll
-    for (int i = 0; i < (KB > 0 ? KB : 1); ++i)
-#pragma unroll
-        for (int r = 0; r < NR; ++r) acc[i][r] = 0.0;
-#pragma unroll
-    for (int t = 0; t < NT3; ++t) tri[t] = 0.0;
-    stream_loop<U>(n >> 1, [&](auto uc, size_t i0, size_t st) {
-        constexpr int UU = decltype(uc)::value;
-        double2 rv[NR][UU];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            if (r < nr) {
-#pragma unroll
-                for (int u = 0; u < UU; ++u) rv[r][u] = ld2<LDNT>(Rv + (size_t)r * ldv, i0 + u * st);
-            } else {
-#pragma unroll
-                for (int u = 0; u < UU; ++u) rv[r][u] = make_double2(0.0, 0.0);
-            }
-        }
-        if (TRI) {
-#pragma unroll
-            for (int r = 0; r < NR; ++r)
-#pragma unroll
-                for (int c = r; c < NR; ++c) {
-                    double a = tri[TRI ? r * NR - r * (r - 1) / 2 + (c - r) : 0];
-#pragma unroll
-                    for (int u = 0; u < UU; ++u) { a = fma(rv[r][u].x, rv[c][u].x, a); a = fma(rv[r][u].y, rv[c][u].y, a); }
-                    tri[TRI ? r * NR - r * (r - 1) / 2 + (c - r) : 0] = a;
-                }
-        }
-#pragma unroll
-        for (int i = 0; i < KB; ++i) {
-            if (i < kb) {
-                double2 vv[UU];
-#pragma unroll
-                for (int u = 0; u < UU; ++u) vv[u] = ld2<LDNT>(V + (size_t)i * ldv, i0 + u * st);
-#pragma unroll
-                for (int r = 0; r < NR; ++r)
-#pragma unroll
-                    for (int u = 0; u < UU; ++u) { acc[i][r] = fma(vv[u].x, rv[r][u].x, acc[i][r]); acc[i][r] = fma(vv[u].y, rv[r][u].y, acc[i][r]); }
-            }
-        }
-    });
-    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        double rl[NR];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) rl[r] = r < nr ? Rv[(size_t)r * ldv + n - 1] : 0.0;
-        if (TRI) {
-#pragma unroll
-            for (int r = 0; r < NR; ++r)
-#pragma unroll
-                for (int c = r; c < NR; ++c) tri[TRI ? r * NR - r * (r - 1) / 2 + (c - r) : 0] = fma(rl[r], rl[c], tri[TRI ? r * NR - r * (r - 1) / 2 + (c - r) : 0]);
-        }
-#pragma unroll
-        for (int i = 0; i < KB; ++i)
-            if (i < kb) {
-                const double vl = V[(size_t)i * ldv + n - 1];
-#pragma unroll
-                for (int r = 0; r < NR; ++r) acc[i][r] = fma(vl, rl[r], acc[i][r]);
-            }
-    }
-    constexpr int NV = KB * NR + (TRI ? NR * (NR + 1) / 2 : 0);
-    __shared__ double sm[4][NV];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < KB; ++i)
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const double s_ = wave_sum(acc[i][r]);
-            if (lane == 0) sm[wid][i * NR + r] = s_;
-        }
-    if (TRI) {
-#pragma unroll
-        for (int t = 0; t < NT3; ++t) {
-            const double s_ = wave_sum(tri[t]);
-            if (lane == 0) sm[wid][KB * NR + t] = s_;
-        }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < NV; j += kThreads)
-        partials[(size_t)blockIdx.x * NV + j] = (sm[0][j] + sm[1][j]) + (sm[2][j] + sm[3][j]);
+    block_dots_body<KB, TRI, U, LDNT, NRT>(n, V, ldv, kb, Rv, nr, partials);
 }
 
 // Pass 2 of a block: the s new basis vectors in place over the block vectors,
@@ -1107,7 +1050,7 @@ int v_minres_update2(bk_ctx* ctx, size_t n, double cza, const double* za, double
 }
 
 int v_nrminf(bk_ctx* ctx, size_t n, const double* x, double* out) {
-    const int grid = grid_for(n, 1, kRedBlocks);
+    const int grid = grid_for(n, 2 * 4, kRedBlocks);        // absmax_kernel: 4 items of 2 elements per lane and iteration
     {
         ProfScope ps(ctx, "blas1", 8.0 * n);
         hipLaunchKernelGGL(absmax_kernel, dim3(grid), dim3(kThreads), 0, ctx->stream, n, x, ctx->d_partials);
@@ -1254,7 +1197,8 @@ int v_multidot_gram(bk_ctx* ctx, size_t n, const double* V, size_t ldv, int k, c
 // ---- block Arnoldi step (sstep.h): pass 1 -- D[i * 8 + r] = <V_i, rhs_r> for the k_old measured basis vectors, T = the packed
 // upper triangle of the right-hand vectors' own dots; rhs_r = basis slot r0 + r, r < nr.  The first launch carries the triangle
 // and up to 4 basis vectors, every further one 8 basis vectors (register budget: 68 / 64 accumulators); the right-hand vectors are
-// re-read by every launch.  One global reduction (and host synchronisation) per launch.
+// re-read by every launch.  One global reduction (and host synchronisation) per launch.  With at most 5 (block_dots_nr5) or 6
+// (block_dots_wide) right-hand vectors and more than 4 basis vectors the first launch carries 8 basis vectors.
 bool v_block_ok(bk_ctx* ctx, size_t n, const double* V, size_t ldv) { return n >= 2 && aligned16(V) && (ldv % 2 == 0); }
 int v_block_dots(bk_ctx* ctx, size_t n, const double* V, size_t ldv, int kold, int r0, int nr, double* D, double* T) {
     if (kold < 0 || kold > kMaxBasis || nr < 1 || nr > sstep::kR) return set_error(ctx, "v_block_dots: bad sizes");
@@ -1263,7 +1207,11 @@ int v_block_dots(bk_ctx* ctx, size_t n, const double* V, size_t ldv, int kold, i
     const double* Rv = V + (size_t)r0 * ldv;
     int done = 0;                        // measured basis vectors covered by the first launch (the one that carries the triangle)
     constexpr int NR5 = 5;
-    if (nr <= NR5 && kold > 4 && ctx->opt("block_dots_nr5", 1.0) != 0.0) {
+    if (nr > NR5 && nr <= kBlockDotsWideNr && kold > 4 && ctx->opt("block_dots_wide", 1.0) != 0.0) {
+        // six right-hand vectors (a solve's last block of TWO steps after a four-step block): 8 basis vectors and the triangle in one
+        // launch of block_dots_wide.hip instead of (4 + 6) + (4 + 6) streams in two
+        BK_TRY(block_dots_wide(ctx, grid, nt, n, V, ldv, kold, Rv, nr, D, T, &done));
+    } else if (nr <= NR5 && kold > 4 && ctx->opt("block_dots_nr5", 1.0) != 0.0) {
         // few right-hand vectors (a solve's last block is usually ONE step: s = 1, u <= 4): 8 basis vectors and the triangle in one launch
         const int kb = std::min(kold, 8);
         constexpr int NV = 8 * NR5 + NR5 * (NR5 + 1) / 2;

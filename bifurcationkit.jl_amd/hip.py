@@ -1025,9 +1025,10 @@ def newton_native(prob: _PdeProblem, x0: HipVec, p: float, ls: _GMRES, tol=1e-12
 def newton_palc_native(prob: _PdeProblem, z0: BorderedArray, tau: BorderedArray, z_pred: BorderedArray, ds, theta,
                        bls: BorderingBLS, tol=1e-12, max_iterations=25, p_min=-math.inf, p_max=math.inf,
                        norm_inf=False, linesearch=False, alpha=1.0, alphamin=1e-3, callback=None):
-    """newton_palc (src/continuation/Palc.jl:187-305) as one library call, with BorderingBLS or MatrixFreeBLS."""
+    """newton_palc (src/continuation/Palc.jl:187-305) as one library call, with BorderingBLS or MatrixFreeBLS.  ``z_pred`` is only
+    read (bk_newton_palc_from): the library copies it into the result only where the corrector has to run in place."""
     ctx = prob.ctx
-    x = z_pred.u.copy()
+    x = z_pred.u.similar()
     p = C.c_double(z_pred.p)
     pv = prob._pvec(z_pred.p)
     arr = (C.c_double * len(pv))(*pv)
@@ -1039,10 +1040,10 @@ def newton_palc_native(prob: _PdeProblem, z0: BorderedArray, tau: BorderedArray,
     lo = bls.solver._opts()
     res = L.NewtonResult()
     big = 1.7e308
-    ctx.check(ctx.lib.bk_newton_palc(
-        ctx.h, prob.h, _ptr(x.t), C.byref(p), _ptr(z0.u.t), float(z0.p), _ptr(tau.u.t), float(tau.p), float(ds),
+    ctx.check(ctx.lib.bk_newton_palc_from(
+        ctx.h, prob.h, _ptr(z_pred.u.t), _ptr(x.t), C.byref(p), _ptr(z0.u.t), float(z0.p), _ptr(tau.u.t), float(tau.p), float(ds),
         float(theta), arr, len(pv), prob.ipar, max(float(p_min), -big), min(float(p_max), big), C.byref(no),
-        C.byref(bo), C.byref(lo), bls.solver._pl(), C.byref(res)), "bk_newton_palc")
+        C.byref(bo), C.byref(lo), bls.solver._pl(), C.byref(res)), "bk_newton_palc_from")
     return dict(u=BorderedArray(x, p.value), converged=bool(res.converged), itnewton=res.itnewton,
                 itlineartot=res.itlinear, residuals=[res.residuals[i] for i in range(res.itnewton + 1)])
 

@@ -409,6 +409,16 @@ int bk_newton_palc(bk_ctx* ctx, bk_problem* prob, double* x, double* p, const do
                    const double* params, int nparams, int ipar, double p_min, double p_max,
                    const bk_newton_opts* nopts, const bk_bordering_opts* bopts,
                    const bk_gmres_opts* lsopts, bk_precond* pl, bk_newton_result* res);
+/* The same corrector from a predictor x0 that is only read: x receives the corrected point (x0 itself when no iteration runs)
+ * and must not overlap x0 unless x == x0, which is bk_newton_palc.  With BorderingBLS, check_precision off and no line search the
+ * first iteration reads x0 and its update writes x, so the predictor is never copied (context option "palc_entry_copy" = 1, or
+ * "palc_fuse_update" = 0: copy first and run in place; so do the line search, check_precision and MatrixFreeBLS).  Same results
+ * bit for bit either way.                                                                                                      */
+int bk_newton_palc_from(bk_ctx* ctx, bk_problem* prob, const double* x0, double* x, double* p,
+                        const double* z0u, double z0p, const double* tauu, double taup, double ds,
+                        double theta, const double* params, int nparams, int ipar, double p_min,
+                        double p_max, const bk_newton_opts* nopts, const bk_bordering_opts* bopts,
+                        const bk_gmres_opts* lsopts, bk_precond* pl, bk_newton_result* res);
 
 /* ------------------------------------------------------------------ complex shifts (Hopf) ----------
  * The Hopf normal form and the minimally augmented Hopf system call the same plugin surface with a COMPLEX shift on
