@@ -8,7 +8,7 @@
     monodromy of a non-orbit is as good an operator to time; recorded).  Warm buffers, ONE synchronisation per timed call,
     `reps` timed calls, median and spread (min, max) reported;
   * the GMRES counts of both, rtol 1e-9, IterativeSolvers flavor;
-  * kernel time of monodromy_march_kernel and monodromy_timesolve_kernel from the library's event scopes, with the algorithmic
+  * kernel time of the monodromy's marching pass and time solve (scopes monodromy_march, monodromy_timesolve), with the algorithmic
     bytes over time (march: u, y read, out written = 3 x 8 K N; time solve: one read and one write of the spectrum = 2 x 8 K N).
 
 Usage: python scripts/floquet_probe.py [--out profiles/floquet_probe.jsonl] [--reps 15] [--sizes 41x21,256x256]

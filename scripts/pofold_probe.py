@@ -2,8 +2,8 @@
 """Measurements of the fold-of-limit-cycles layer, one process, appended to profiles/pofold_probe.jsonl.  Per size
 (16 x 12, M = 12 -- the fold run of the tests -- and 41 x 21, M = 30, the example's grid):
 
-  * kernel time of potrap_adjoint_march_kernel, pofold_border_kernel and potrap_adjoint_timesolve_kernel from the library's event
-    scopes with their algorithmic bytes (4 streams of 8 M N bytes for the two marching kernels, 3 for the time solve), next to the
+  * kernel time of the adjoint and fold-border marching passes and of the transposed time solve (scopes potrap_jvp_adjoint,
+    pofold_border, potrap_adjoint_timesolve) from the library's event scopes with their algorithmic bytes (4 streams of 8 M N bytes for the two marching kernels, 3 for the time solve), next to the
     forward potrap_jvp scope;
   * wall time and GMRES count of one doubly bordered solve (rtol 1e-9, IterativeSolvers flavor) next to the plain orbit solve;
   * the fold refinement: continuation_po_trap(save_sol=True, nev=2, detect_bifurcation=2) from dr = 0.15 until the fold is

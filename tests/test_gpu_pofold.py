@@ -159,6 +159,34 @@ def test_adjoint_rows_have_the_same_bits_for_every_chunking_and_aliasing_is_refu
         po.jvp_adjoint(U, 6.0, pv[:5], W, 0.5)
 
 
+def test_fold_border_rows_have_the_same_bits_for_every_chunking(ctx):
+    """bk_potrap_fold_border, lens r, under potrap_chunks = 1, 2, 4, 11 and the default at 16 x 12, M = 12 (K = 11: C = 11, 6 / 5,
+    3 / 3 / 3 / 2, 1): every chunking gives sigx of the single chunk bit for bit; (sigma_x)_T and sigma_p, reduced over another set
+    of workgroups, stay within the summation bound 4 n eps sum |terms| of the long-double restatement, the bound of
+    test_fold_border_matches_extended_precision."""
+    hip, po_ = _mods()
+    dims, M = (16, 12), 12
+    m = _model(dims)
+    d, pars, po = _setup(ctx, dims, M)
+    U, W, V = po.vec(d["U"]), po.vec(d["W"]), po.vec(d["X"])
+    vT = d["dT"]
+    res = {}
+    try:
+        for k in (1.0, 2.0, 4.0, 11.0, 0.0):
+            ctx.set_option("potrap_chunks", k)
+            sx, sp = po.fold_border(U, d["T"], _pv(pars), R.PNAMES.index("r"), hip.BorderedArray(V, vT), W)
+            res[k] = (sx.u.numpy(), sx.p, sp)
+    finally:
+        ctx.set_option("potrap_chunks", 0.0)
+    L = lambda a: a.astype(LD)
+    _, rT, rp = F.fold_border(m, L(d["U"]), d["T"], pars, "r", L(d["X"]), vT, L(d["W"]))
+    _, uT, up = F.fold_border(m, d["U"], d["T"], pars, "r", d["X"], vT, d["W"], mod=True)
+    for k, (sx, sT, sp) in res.items():
+        assert np.array_equal(sx, res[1.0][0]), k
+        probe(f"pofold.border_chunks_T.{int(k)}", abs(sT - float(rT)) / (4 * po.n * EPS * uT), 1.0)
+        probe(f"pofold.border_chunks_p.{int(k)}", abs(sp - float(rp)) / (4 * po.n * EPS * up), 1.0)
+
+
 # ------------------------------------------------------------------------------------------ the adjoint preconditioner
 @functools.lru_cache(maxsize=None)
 def _precond_reference(dims, M):
