@@ -99,6 +99,7 @@ struct bk_ctx {
     struct Diag {
         double block_steps = 0.0, block_truncated = 0.0, block_unconsumed = 0.0;    // operator applications issued in blocks / void tails / speculated past convergence
         double last_orth_defect = 0.0, last_orth_estimate = 0.0;                   // option orth_probe
+        double block_folded = 0.0, chunk_handover = 0.0;                           // cycles whose solution update folded a deferred block in / cycles handed from the blocks to the device chunks
         double check_mismatch = 0.0;                                               // explicit residual checks that contradicted the Arnoldi estimate (stencil-free form)
         double fold_unconverged = 0.0;                                             // bk_newton_fold: bordered-vector / step solves that returned unconverged
         double hopf_unconverged = 0.0;                                             // bk_newton_hopf: the same count for the Hopf system
@@ -114,6 +115,8 @@ struct bk_ctx {
         if (key == "gmres_block_unconsumed") return &diag.block_unconsumed;
         if (key == "gmres_last_orth_defect") return &diag.last_orth_defect;
         if (key == "gmres_last_orth_estimate") return &diag.last_orth_estimate;
+        if (key == "gmres_block_folded") return &diag.block_folded;
+        if (key == "gmres_chunk_handover") return &diag.chunk_handover;
         if (key == "gmres_check_mismatch") return &diag.check_mismatch;
         if (key == "fold_unconverged_solves") return &diag.fold_unconverged;
         if (key == "hopf_unconverged_solves") return &diag.hopf_unconverged;

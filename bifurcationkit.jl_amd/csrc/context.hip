@@ -551,6 +551,7 @@ void ctx_lane_merge(bk_ctx* ctx, bk_ctx* lane) {
     lane->prof_entries.clear();
     ctx->diag.block_steps += lane->diag.block_steps; ctx->diag.block_truncated += lane->diag.block_truncated;
     ctx->diag.block_unconsumed += lane->diag.block_unconsumed; ctx->diag.check_mismatch += lane->diag.check_mismatch;
+    ctx->diag.block_folded += lane->diag.block_folded; ctx->diag.chunk_handover += lane->diag.chunk_handover;
     lane->diag = bk_ctx::Diag();
     if (!lane->block_log.empty()) {
         for (size_t i = 0; i < lane->block_log.size(); ++i) {

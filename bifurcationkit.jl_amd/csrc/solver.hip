@@ -453,6 +453,7 @@ int gmres_core(bk_ctx* ctx, bk_op* A, const double* b, const double* bt, double*
             // hand the rest of the cycle to the device-resident chunks (two-pass policy: the device has no Gram matrix of this basis, its
             // defect estimate starts at the tolerance, i.e. on the safe side -- what the host path does in the same situation)
             blocks_done = true;
+            ctx->diag.chunk_handover += 1.0;
             dev_gram = false;
             q_count = 0;
             const double ot = B.orth_tol;
@@ -671,6 +672,7 @@ int gmres_core(bk_ctx* ctx, bk_op* A, const double* b, const double* bt, double*
         if (pend.active && k > pend.k) {
             // the solve (or the cycle) ends inside the deferred block: c of its vectors carry solution coefficients
             std::vector<double> cf(k, 0.0);
+            ctx->diag.block_folded += 1.0;
             sstep::fold_solution_coefficients(pend.k, k - pend.k, pend.Cm, pend.Tm, yk.data(), cf.data());
             BK_TRY(v_multiaxpy(ctx, n, B.V, B.ld, k, cf.data(), x_zero ? nullptr : x, 1.0, x, nullptr));
         } else {
