@@ -243,6 +243,18 @@ SIGNATURES = {
     "bk_bautin_contract": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, VP, c_double_p]),
     "bk_bautin_normal_form": (I, [VP, VP, VP, c_double_p, I, D, VP, VP, VP, VP, VP, VP, VP, c_double_p, C.POINTER(GmresOpts), VP,
                                   VP, VP, VP, VP, VP, VP, VP, c_double_p, c_int_p, c_int_p]),
+    "bk_bt_border": (I, [VP, VP, c_double_p, I, I, I, D, VP, VP, VP, VP, VP, VP, c_double_p]),
+    "bk_bt_terms": (I, [VP, VP, VP, c_double_p, I, VP, VP, C.POINTER(GmresOpts), VP, VP, VP, VP, VP, VP, c_double_p, c_int_p,
+                        c_int_p]),
+    "bk_bt_linsolve": (I, [VP, VP, VP, c_double_p, I, I, I, VP, VP, VP, VP, VP, c_double_p, C.POINTER(GmresOpts), VP, VP,
+                           c_double_p, c_int_p, c_int_p]),
+    "bk_newton_bt": (I, [VP, VP, VP, c_double_p, c_double_p, I, I, I, VP, VP, C.POINTER(NewtonOpts), C.POINTER(GmresOpts), VP, VP,
+                         VP, VP, VP, VP, c_double_p, C.POINTER(NewtonResult), c_int_p, c_int_p]),
+    "bk_bt_nf_dots": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP, c_double_p]),
+    "bk_bt_nf_rhs": (I, [VP, VP, c_double_p, I, I, D, VP, VP, VP, VP]),
+    "bk_bt_nf_k2": (I, [VP, VP, c_double_p, I, I, I, VP, VP, c_double_p]),
+    "bk_bt_normal_form": (I, [VP, VP, VP, c_double_p, I, I, I, VP, VP, VP, VP, I, C.POINTER(GmresOpts), VP, VP, VP, VP, VP,
+                              c_double_p, c_int_p, c_int_p]),
     "bk_d3f": (I, [VP, VP, c_double_p, I, VP, VP, VP, VP]),
     "bk_nf1d_dots": (I, [VP, VP, c_double_p, I, I, VP, VP, c_double_p]),
     "bk_nf1d_rhs": (I, [VP, VP, c_double_p, I, I, VP, D, D, VP, VP]),

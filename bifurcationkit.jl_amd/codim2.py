@@ -25,9 +25,11 @@ regular at the fold, where J \\ a and J \\ F do not converge (context option fol
 
 Codim-2 points: on Hopf curves generalised Hopf (Bautin) points are detected, bisected and given their normal form
 (continuation_hopf(..., detect_codim2 = 1 | 2), get_normal_form on a "gh" point); on fold curves cusp points, the same way
-(continuation_fold(..., detect_codim2 = 1 | 2), get_normal_form on a "cusp" point).  Bogdanov-Takens, zero-Hopf and Hopf-Hopf
-points are not located (BT and omega are recorded per point, and a Hopf curve stops near omega = 0); for the Swift-Hohenberg
-problems J' = J, so BT = <zeta*, zeta> = 1 and a fold curve has no Bogdanov-Takens point.
+(continuation_fold(..., detect_codim2 = 1 | 2), get_normal_form on a "cusp" point).  A Hopf curve that stops near omega = 0 records
+a Bogdanov-Takens guess ("bt"), which newton_bt refines and get_normal_form unfolds (a, b, K10, K11, K2; the last section of this
+module); the Hopf curve restarts from it with continuation_hopf_from_bt.  Zero-Hopf and Hopf-Hopf points are not located, nor
+Bogdanov-Takens points on fold curves; for the Swift-Hohenberg problems J' = J, so BT = <zeta*, zeta> = 1 and a fold curve has no
+Bogdanov-Takens point.
 
 What the two formulations have in common is written once: _MinAugProblem (the cached bordered vectors and the problem surface),
 _MinAugLinearSolver, _continuation_minaug (the PALC loop) and _newton_minaug_mirror (the Newton loop of the mirrors).
@@ -1037,7 +1039,9 @@ def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls
     br.l1 (b) and br.GH (Re b; the previous value when |Re b| >= 1e5, :632), and every sign change of GH between consecutive
     points goes to br.specialpoint as type "gh" with the bracketing p2 interval.  2: each sign change is bisected along the curve
     (_locate_gh) and the special point keeps the located state; the curve continues from the state it had before the bisection,
-    so the recorded points are those of detect_codim2 = 1.  Bogdanov-Takens, zero-Hopf and Hopf-Hopf points are not located.
+    so the recorded points are those of detect_codim2 = 1.  With 1 or 2, a run that ends at |omega| < 100 tol appends a special
+    point of type "bt" with the stop state (x, p1, omega), p2, the step index and the current a, b: a fold point NEAR the
+    Bogdanov-Takens point, the guess newton_bt refines (bt_point).  Zero-Hopf and Hopf-Hopf points are not located.
 
     ``bls`` (optional): the bordered solver of the formulation's bordered vectors -- MatrixFreeBLS(ls, use_pl=True) takes each from
     ONE preconditioned bordered solve (option hopf_bordered).  The PALC border and the Newton step of G stay as they are."""
@@ -1047,9 +1051,12 @@ def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls
     if detect_codim2 and update_minaug_every_step != 1:
         raise ValueError("detect_codim2 needs the bordered vectors of every point (update_minaug_every_step = 1)")
 
+    last = {}
+
     def record_x(X, om, tau):
         br.p1.append(float(X.p[0])); br.omega.append(float(X.p[1])); br.BT.append(om)
         if detect_codim2:
+            last["X"] = X                           # the state of the loop, read once more if the curve stops at omega = 0
             with _solver_state_kept(prob.ctx):
                 l1 = _first_lyapunov(P, X)
             br.l1.append(l1)
@@ -1072,6 +1079,13 @@ def continuation_hopf(prob, hopf_guess: HopfVec, p2: float, lens2: str, a, b, ls
         P, HopfLinearSolverMinAug(), "Hopf", br, hopf_guess, p2, cp, theta, normC, update_minaug_every_step, save_sol, ds_sequence,
         verbosity, record_x, skipped=lambda X: float(X.p[1]), describe=lambda X: f"p1={X.p[0]:+.8f} omega={X.p[1]:+.8f}",
         stop_after=lambda om: abs(om) < thresh_bt, after_record=after_record if detect_codim2 else None)
+    if br.stopped_at_bt and detect_codim2:
+        # the :bt point of the reference (src/events/Event.jl:27-40, MinAugHopf.jl:353-367): the state at which the event value
+        # fell below threshBT.  The Hopf Newton has collapsed onto omega = 0 there, so this is a fold point NEAR the
+        # Bogdanov-Takens point and the guess of newton_bt (bt_point), not the point itself.
+        X, i = last["X"], len(br.p2) - 1
+        br.specialpoint.append(dict(type="bt", idx=i, step=i, p1=float(X.p[0]), p2=float(br.p2[i]), omega=float(X.p[1]),
+                                    x=X.u.copy(), a=tuple(v.copy() for v in P.a), b=tuple(v.copy() for v in P.b), status="guess"))
     return br
 
 
@@ -1601,7 +1615,7 @@ def _cusp_from_branch(br, ind: int, prob, ls: _GMRES, tol, max_iterations, norm_
 
 
 def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, max_iterations=15, norm_inf=False, seed=0,
-                    bls=None, refine=True):
+                    bls=None, refine=True, ls_adj=None, detailed=True):
     """get_normal_form(br, ind) (src/NormalForms.jl:1102-1204) for a point of type "hopf" of a branch of
     continuation.continuation_native(..., bisection = True, save_sol = True): hopf_point -> hopf_start_vectors (the reference's
     random start, or start_with_eigen when ``eig`` is given) -> newton_hopf_native -> hopf_eigenpair -> hopf_normal_form_native.
@@ -1613,12 +1627,17 @@ def get_normal_form(br, ind: int, prob, ls: _GMRES, eig=None, nev=4, tol=1e-10, 
     solver of newton_hopf_native and bautin_normal_form_native (MatrixFreeBLS(ls, use_pl=True): option hopf_bordered).  A point of
     type "cusp" of a FoldBranch (continuation_fold(..., detect_codim2 > 0)) returns its Cusp record: newton_fold_native in lens1 at
     the located p2 -> q = v / |v|, p = w / <q, w> -> cusp_normal_form_native, ``bls`` the bordered solver of both
-    (MatrixFreeBLS(ls, use_pl=True): option fold_bordered)."""
+    (MatrixFreeBLS(ls, use_pl=True): option fold_bordered).  A point of type "bt" of a HopfBranch (a curve of
+    continuation_hopf(..., detect_codim2 > 0) that stopped at omega = 0) returns its BogdanovTakens record: newton_bt_native from
+    the recorded state -> bt_jordan_basis -> bogdanov_takens_normal_form_native (``detailed = False``: a and b only); ``ls_adj`` is
+    the solver with the preconditioner of the adjoint operator (bt_adjoint_solver), required there."""
     from . import normal_form1d as N1
     sh = N1.is_sh_problem(prob)                     # decided before the branch is looked at
     kind = br.specialpoint[ind].get("type")
     if kind == "gh" and isinstance(br, HopfBranch):
         return _bautin_from_branch(br, ind, prob, ls, tol, max_iterations, norm_inf, bls)
+    if kind == "bt" and isinstance(br, HopfBranch):
+        return _bt_from_branch(br, ind, prob, ls, ls_adj, tol, max_iterations, norm_inf, seed=seed, detailed=detailed)
     if kind == "cusp" and isinstance(br, FoldBranch):
         return _cusp_from_branch(br, ind, prob, ls, tol, max_iterations, norm_inf, bls)
     if sh and kind in ("bp", "fold"):
@@ -1664,7 +1683,15 @@ class HopfOrbit:
         return self.at([2.0 * math.pi * m / M for m in range(int(M))])
 
 
-def predictor(hopf, ds: float, ampfactor=1.0):
+def predictor(point, *args, **kw):
+    """predictor(bp, ds; ampfactor) for a SimpleBranchPoint or Hopf record (below), predictor(bt, "HopfCurve" | "FoldCurve", ds) for
+    a BogdanovTakens record (bt_predictor)."""
+    if isinstance(point, BogdanovTakens):
+        return bt_predictor(point, *args, **kw)
+    return _predictor_codim1(point, *args, **kw)
+
+
+def _predictor_codim1(hopf, ds: float, ampfactor=1.0):
     """predictor(bp, ds; ampfactor).  A SimpleBranchPoint record goes to normal_form1d.predictor (:389-531).  For a Hopf record,
     predictor(hp::Hopf, ds; ampfactor) (:1227-1281): dict(orbit, Psi001, amp, omega, period, p, dsfactor).  With the
     coefficients a, b the side of the Hopf point where the orbits live is dsfactor = +1 when Re a Re b < 0, else -1,
@@ -1689,3 +1716,384 @@ def predictor(hopf, ds: float, ampfactor=1.0):
         P001 = P110 = P200 = None
     return dict(orbit=HopfOrbit(hopf, ds, amp, P001, P110, P200), Psi001=P001, amp=2 * amp, omega=omega,
                 period=abs(2 * math.pi / omega), p=pnew, dsfactor=dsfactor)
+
+
+# ------------------------------------------------------------------------------------------ Bogdanov-Takens points
+# src/codim2/MinAugBT.jl and the Bogdanov-Takens part of src/codim2/NormalForms.jl on CGL2d, matrix-free.  J has a double zero
+# eigenvalue at the point, so every solve is ONE preconditioned bordered GMRES (MatrixFreeBLS(ls, use_pl=True) semantics); the
+# solves with J' take ``ls_adj``, the same solver with the preconditioner of the adjoint operator (bt_adjoint_solver).
+#
+#   bt_point / bt_start_vectors   the guess a Hopf curve records where it stops at omega = 0, and the reference's default a, b
+#   bt_terms, bt_border           the bordered vectors (bk_bt_terms) and the fused pass for sigma_x, sigma_p / A12, A22 (bk_bt_border)
+#   newton_bt / newton_bt_native  newton_bt call by call, and as one library call (bk_newton_bt)
+#   bt_jordan_basis               (q0, q1), (p0, p1) of NormalForms.jl:603-622
+#   bogdanov_takens_normal_form / _native    a, b, gamma, c, K10, K11, K2 (:180-272), call by call and as bk_bt_normal_form
+#   predictor(bt, "HopfCurve" | "FoldCurve", ds)   (:342-434);  continuation_hopf_from_bt: the Hopf curve restarted from the point
+BTVec = HopfVec                                  # (u, p) with p = [p1, p2]
+
+
+def bt_adjoint_solver(prob, ls: _GMRES, a: float, b: float):
+    """``ls`` with the left preconditioner of the adjoint operator: L0' = Lap (x) I_2 + [[a, b], [-b, a]], the cGL block of
+    CGLBlockPreconditioner(prob, a, b) with the sign of its rotation part flipped."""
+    import copy
+    from .hip import CGLBlockPreconditioner
+    out = copy.copy(ls)
+    out.Pl = CGLBlockPreconditioner(prob, a, -b)
+    return out
+
+
+def _bt_lenses(prob, lens2):
+    if lens2 == prob.lens:
+        raise ValueError(f"Please choose 2 different parameters. You only passed {lens2}")
+    return prob.param_names.index(prob.lens), prob.param_names.index(lens2)
+
+
+def _bt_pvec(prob, lens2, p):
+    return _params(prob, **{prob.lens: float(p[0]), lens2: float(p[1])})
+
+
+def bt_border(prob, x: HipVec, pars, ipar1: int, ipar2: int, s: float, v1: HipVec, v2: HipVec, w1: HipVec, w2: HipVec):
+    """One fused pass (bk_bt_border): (row1, row2, block) with row1 = s B(x)[v1, .]' w1, row2 = s (B(x)[v1, .]' w2 + B(x)[v2, .]' w1)
+    and block[i, k] = s <w1, D_k v1> (i = 0), s (<w2, D_k v1> + <w1, D_k v2>) (i = 1) for the lenses k = (ipar1, ipar2)."""
+    ctx = prob.ctx
+    r1, r2 = x.similar(), x.similar()
+    out = (C.c_double * 4)()
+    ctx.check(ctx.lib.bk_bt_border(prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar1), int(ipar2), float(s), _ptr(v1.t),
+                                   _ptr(v2.t), _ptr(w1.t), _ptr(w2.t), _ptr(r1.t), _ptr(r2.t), out), "bk_bt_border")
+    return r1, r2, np.array(list(out)).reshape(2, 2)
+
+
+def bt_terms(prob, x: HipVec, pars, a: HipVec, b: HipVec, ls: _GMRES, ls_adj: _GMRES | None, which="vw"):
+    """bk_bt_terms: dict(v1, v2, sigma, w1, w2, converged, itlinear) -- the pair (v1, v2) with sigma when ``which`` has "v", the
+    pair (w1, w2) when it has "w" (needs ``ls_adj``, refused with a message when missing); converged / itlinear per solve in the
+    order v1, v2, w1, w2."""
+    ctx = prob.ctx
+    v = (x.similar(), x.similar()) if "v" in which else (None, None)
+    w = (x.similar(), x.similar()) if "w" in which else (None, None)
+    sg = (C.c_double * 2)()
+    cv, it = (C.c_int * 4)(), (C.c_int * 4)()
+    lo = ls._opts()
+    ctx.check(ctx.lib.bk_bt_terms(ctx.h, prob.h, _ptr(x.t), _carr(pars), len(pars), _ptr(a.t), _ptr(b.t), C.byref(lo), ls._pl(),
+                                  ls_adj._pl() if ls_adj is not None else None, _cptr(v[0]), _cptr(v[1]), _cptr(w[0]),
+                                  _cptr(w[1]), sg, cv, it), "bk_bt_terms")
+    return dict(v1=v[0], v2=v[1], w1=w[0], w2=w[1], sigma=(sg[0], sg[1]) if "v" in which else None,
+                converged=[bool(c) for c in cv], itlinear=list(it))
+
+
+def bt_point(br, ind: int) -> BTVec:
+    """bt_point(br, index) (MinAugBT.jl:59-65): the recorded stop state of the Hopf curve as BTVec(x, [p1, p2])."""
+    sp = br.specialpoint[ind]
+    if sp.get("type") != "bt":
+        raise ValueError(f"This should be a BT point.\nYou passed a {sp.get('type')} point.")
+    return BTVec(sp["x"].copy(), [sp["p1"], sp["p2"]])
+
+
+def bt_start_vectors(prob, X: BTVec, lens2: str, ls: _GMRES, ls_adj: _GMRES, seed=0):
+    """(a, b) of newton_bt(br, ind) without start_with_eigen (:417-435): random a, b, then a = w1 / |w1|, b = v1 / |v1| of the
+    bordered solves at the guess."""
+    rng = np.random.default_rng(seed)
+    x = X.u
+    a = HipVec.from_numpy(prob.ctx, rng.random(x.n), x.nglobal)
+    b = HipVec.from_numpy(prob.ctx, rng.random(x.n), x.nglobal)
+    t = bt_terms(prob, x, _bt_pvec(prob, lens2, X.p), a, b, ls, ls_adj)
+    return t["w1"].scale_(1.0 / t["w1"].norm()), t["v1"].scale_(1.0 / t["v1"].norm())
+
+
+def _norm_bt(F, sigma, norm_inf):
+    if norm_inf:
+        return _nanmax(F.norminf(), abs(sigma[0]), abs(sigma[1]))
+    return math.sqrt(F.norm() ** 2 + sigma[0] ** 2 + sigma[1] ** 2)
+
+
+def newton_bt(prob, guess: BTVec, lens2: str, a: HipVec, b: HipVec, ls: _GMRES, ls_adj: _GMRES, tol=1e-10, max_iterations=25,
+              norm_inf=False):
+    """newton_bt with BTLinearSolverMinAug under _newton, call by call: per point bk_bt_terms for (v1, v2, sigma) and the residual;
+    per step bk_bt_terms for (w1, w2), one bk_bt_border pass (s = -1) for sigma_x and sigma_p, and ONE block-bordered solve
+    MatrixFreeBLS(ls, use_pl=True).solve_block(J, (dp1F, dp2F), (sigma1_x, sigma2_x), sigma_p, F, sigma)."""
+    i1, i2 = _bt_lenses(prob, lens2)
+    if ls_adj is None or ls_adj._pl() is None:
+        raise TypeError("newton_bt needs ls_adj, the solver with the left preconditioner of the adjoint operator (bt_adjoint_solver)")
+    bls = MatrixFreeBLS(ls, use_pl=True)
+    x, p = guess.u.copy(), np.array(guess.p, dtype=np.float64)
+    its, bad = [0] * 5, 0
+    state = {}
+
+    def point():
+        nonlocal bad
+        pv = _bt_pvec(prob, lens2, p)
+        t = bt_terms(prob, x, pv, a, b, ls, None, "v")
+        its[0] += t["itlinear"][0]; its[1] += t["itlinear"][1]
+        bad += sum(not c for c in t["converged"][:2])
+        state["pv"] = pv
+        return residual(prob, x, pv), t["sigma"], t["v1"], t["v2"]
+
+    def update(F, sigma, v1, v2):
+        nonlocal bad
+        pv = state["pv"]
+        t = bt_terms(prob, x, pv, a, b, ls, ls_adj, "w")
+        r1, r2, sp = bt_border(prob, x, pv, i1, i2, -1.0, v1, v2, t["w1"], t["w2"])
+        J = HipJacobian(prob, x, pv)
+        dX, dp, cv, it = bls.solve_block(J, (dpF(prob, x, pv, i1), dpF(prob, x, pv, i2)), (r1, r2), sp, F, sigma)
+        its[2] += t["itlinear"][2]; its[3] += t["itlinear"][3]; its[4] += it
+        bad += sum(not c for c in t["converged"][2:]) + (0 if cv else 1)
+        state["w"] = (t["w1"], t["w2"])
+        x.add_(dX, -1.0)
+        p[0] -= dp[0]
+        p[1] -= dp[1]
+
+    (F, sigma, v1, v2), res, step = _newton_minaug_mirror(point, update, lambda F, sg: _norm_bt(F, sg, norm_inf), tol, max_iterations)
+    w1, w2 = state.get("w", (None, None))
+    return dict(u=BTVec(x, p), converged=res[-1] < tol, itnewton=step, itlineartot=sum(its), itsolves=its, residuals=res, v1=v1,
+                v2=v2, w1=w1, w2=w2, sigma=sigma, unconverged_solves=bad)
+
+
+def newton_bt_native(prob, guess: BTVec, lens2: str, a: HipVec, b: HipVec, ls: _GMRES, ls_adj: _GMRES, tol=1e-10,
+                     max_iterations=25, norm_inf=False, callback=None):
+    """The same as one library call (bk_newton_bt).  The double zero eigenvalue of J at the returned point moves like the square
+    root of what the last update leaves, the error of the linear solves included: give ``ls`` an rtol well below ``tol`` (the tests
+    run 1e-13 under tol = 1e-10 and find |lambda| <= 5e-7)."""
+    i1, i2 = _bt_lenses(prob, lens2)
+    ctx = prob.ctx
+    x = guess.u.copy()
+    p = (C.c_double * 2)(float(guess.p[0]), float(guess.p[1]))
+    pv = _bt_pvec(prob, lens2, guess.p)
+    v1, v2, w1, w2 = x.similar(), x.similar(), x.similar(), x.similar()
+    sigma = (C.c_double * 2)()
+    its, bad = (C.c_int * 5)(), C.c_int()
+    no = newton_opts(tol, max_iterations, norm_inf, callback=callback)
+    lo = ls._opts()
+    res = L.NewtonResult()
+    ctx.check(ctx.lib.bk_newton_bt(ctx.h, prob.h, _ptr(x.t), p, _carr(pv), len(pv), i1, i2, _ptr(a.t), _ptr(b.t), C.byref(no),
+                                   C.byref(lo), ls._pl(), ls_adj._pl() if ls_adj is not None else None, _ptr(v1.t), _ptr(v2.t),
+                                   _ptr(w1.t), _ptr(w2.t), sigma, C.byref(res), its, C.byref(bad)), "bk_newton_bt")
+    return dict(u=BTVec(x, [p[0], p[1]]), converged=bool(res.converged), itnewton=res.itnewton, itlineartot=res.itlinear,
+                itsolves=list(its), residuals=[res.residuals[i] for i in range(res.itnewton + 1)], v1=v1, v2=v2,
+                w1=w1 if res.itnewton else None, w2=w2 if res.itnewton else None, sigma=(sigma[0], sigma[1]),
+                unconverged_solves=bad.value)
+
+
+@dataclass
+class BogdanovTakens:
+    """BogdanovTakens (src/NormalForms.jl): x0, params, lens = (lens1, lens2), ipars = the indices of the two lenses in params, zeta = (q0, q1),
+    zeta_star = (p0, p1), newton = the result of the refinement that led here (get_normal_form), nf =
+    dict(a, b[, gamma, c, K10, K11, K2, H2000, H1100, H0010, H0001]) or None, converged / itlinear per solve of the normal form,
+    ``basis`` = the Gram matrices of the Jordan basis (<p_i, q_j>, <p_i, J q_j>)."""
+    x0: HipVec
+    params: list
+    lens: tuple
+    ipars: tuple
+    zeta: tuple
+    zeta_star: tuple
+    nf: dict | None = None
+    converged: list = field(default_factory=list)
+    itlinear: list = field(default_factory=list)
+    basis: tuple | None = None
+    newton: dict | None = None
+
+    @property
+    def p(self):
+        return np.array([self.params[i] for i in self.ipars])
+
+
+def bt_jordan_basis(prob, X: BTVec, lens2: str, vr: HipVec, vl: HipVec, ls: _GMRES, ls_adj: _GMRES) -> BogdanovTakens:
+    """The basis (q0, q1), (p0, p1) of NormalForms.jl:603-622 at X from guesses vr, vl of the right and left null vectors: four
+    bordered solves (two with J, two with J') and the normalisation, J q0 = 0, J q1 = q0, J' p1 = 0, J' p0 = p1,
+    <p_i, q_j> = delta_ij.  Warns, as the reference does (:174-178), when a Gram matrix is off by more than 1e-5."""
+    import warnings
+    i1, i2 = _bt_lenses(prob, lens2)
+    pv = _bt_pvec(prob, lens2, X.p)
+    x = X.u
+    J, Jt = HipJacobian(prob, x, pv), HipJacobian(prob, x, pv, adjoint=True)
+    bl, bla = MatrixFreeBLS(ls, use_pl=True), MatrixFreeBLS(ls_adj, use_pl=True)
+    zero = x.zerovector()
+    cvs, its = [], []
+
+    def run(b_, *args):
+        y, _, cv, it = b_(*args)
+        cvs.append(cv); its.append(it)
+        return y
+
+    q0 = run(bl, J, vl, vr, 0.0, zero, 1.0)
+    p1 = run(bla, Jt, vr, vl, 0.0, zero, 1.0)
+    q1 = run(bl, J, p1, q0, 0.0, q0, 0.0)
+    p0 = run(bla, Jt, q0, p1, 0.0, p1, 0.0)
+    mu = math.sqrt(abs(q0.inner(q0)))
+    q0.scale_(1.0 / mu)
+    q1.scale_(1.0 / mu)
+    q1.add_(q0, -q0.inner(q1))
+    nu = q0.inner(p0)
+    p1.scale_(1.0 / nu)
+    p0.add_(p1, -p0.inner(q1))
+    p0.scale_(1.0 / nu)
+    G = np.array([[ps.inner(q) for q in (q0, q1)] for ps in (p0, p1)])
+    Jq = [J(q0), J(q1)]
+    GJ = np.array([[ps.inner(jq) for jq in Jq] for ps in (p0, p1)])
+    if np.abs(G - np.eye(2)).max() > 1e-5:
+        warnings.warn(f"G == I(2) is not valid. We built a basis such that G = {G}")
+    if np.abs(GJ - np.array([[0.0, 1.0], [0.0, 0.0]])).max() > 1e-5:
+        warnings.warn(f"G is not close to the Jordan block of size 2. We built a basis such that G = {GJ}")
+    return BogdanovTakens(x.copy(), pv, (prob.lens, lens2), (i1, i2), (q0, q1), (p0, p1), None, cvs, its, (G, GJ))
+
+
+def bt_nf_dots(prob, x: HipVec, pars, q0, q1, p0, p1):
+    """One pass (bk_bt_nf_dots): <p1, B00>, <p0, B00>, <p1, B01>, <p0, B01>, <p1, B11>, <p0, B11> with Bij = d2F(x)[qi, qj]."""
+    ctx = prob.ctx
+    out = (C.c_double * 6)()
+    ctx.check(ctx.lib.bk_bt_nf_dots(prob.h, _ptr(x.t), _carr(pars), len(pars), _ptr(q0.t), _ptr(q1.t), _ptr(p0.t), _ptr(p1.t), out),
+              "bk_bt_nf_dots")
+    return list(out)
+
+
+def bt_nf_rhs(prob, x: HipVec, pars, mode: int, k: float, q0: HipVec, q1: HipVec, H: HipVec | None = None) -> HipVec:
+    """One pass (bk_bt_nf_rhs): mode 0: k q1 - B(q0, q0); mode 1: k q1 + H - B(q0, q1)."""
+    return _into_similar(prob, "bk_bt_nf_rhs", x, pars, int(mode), float(k), _ptr(q0.t), _ptr(q1.t), _cptr(H))
+
+
+def bt_nf_k2(prob, x: HipVec, pars, ipar1: int, ipar2: int, p1: HipVec, H0001: HipVec):
+    """One pass (bk_bt_nf_k2): <p1, B(H0001, H0001)>, <p1, D_1 H0001>, <p1, D_2 H0001>."""
+    ctx = prob.ctx
+    out = (C.c_double * 3)()
+    ctx.check(ctx.lib.bk_bt_nf_k2(prob.h, _ptr(x.t), _carr(pars), len(pars), int(ipar1), int(ipar2), _ptr(p1.t), _ptr(H0001.t), out),
+              "bk_bt_nf_k2")
+    return list(out)
+
+
+def _bt_nf_dict(vals, H=None):
+    nf = dict(a=vals[0], b=vals[1])
+    if H is not None:
+        nf.update(gamma=vals[2], c=vals[3], K10=np.array(vals[4:6]), K11=np.array(vals[6:8]), K2=np.array(vals[8:10]),
+                  H2000=H[0], H1100=H[1], H0010=H[2], H0001=H[3])
+    return nf
+
+
+def bogdanov_takens_normal_form(prob, bt: BogdanovTakens, ls: _GMRES, detailed=True) -> BogdanovTakens:
+    """bogdanov_takens_normal_form (NormalForms.jl:141-335) through K2, call by call: bt_nf_dots for a, b (detailed = False returns
+    here), then bt_nf_rhs + MatrixFreeBLS(ls, use_pl=True)(J, p1, q0, 0, rhs, 0) for H2000 and H1100, one bt_border pass (s = +1 on
+    (q0, q1, p1, p0)) for A12 and A22, two solve_block calls for (H0010, K10) and (H0001, K11), bt_nf_k2 for K2.  a and b keep the
+    orientation of the basis as computed.  The coefficients of the homoclinic predictor are not computed."""
+    import dataclasses
+    x, pv = bt.x0, bt.params
+    i1, i2 = bt.ipars
+    (q0, q1), (p0, p1) = bt.zeta, bt.zeta_star
+    d = bt_nf_dots(prob, x, pv, q0, q1, p0, p1)
+    a, b = 0.5 * d[0], d[1] + d[2]
+    if not detailed:
+        return dataclasses.replace(bt, nf=_bt_nf_dict([a, b]), converged=[], itlinear=[])
+    bls = MatrixFreeBLS(ls, use_pl=True)
+    J = HipJacobian(prob, x, pv)
+    cvs, its = [], []
+    H2000, _, cv, it = bls(J, p1, q0, 0.0, bt_nf_rhs(prob, x, pv, 0, 2.0 * a, q0, q1), 0.0)
+    cvs.append(cv); its.append(it)
+    gamma = (-2.0 * p0.inner(H2000) + 2.0 * d[3] + d[4]) / 2.0
+    H2000.add_(q0, gamma)
+    H1100, _, cv, it = bls(J, p1, q0, 0.0, bt_nf_rhs(prob, x, pv, 1, b, q0, q1, H2000), 0.0)
+    cvs.append(cv); its.append(it)
+    c = 3.0 * p0.inner(H1100) - d[5]
+    r1, r2, A22 = bt_border(prob, x, pv, i1, i2, 1.0, q0, q1, p1, p0)
+    J1s = (dpF(prob, x, pv, i1), dpF(prob, x, pv, i2))
+    H0010, K10, cv, it = bls.solve_block(J, J1s, (r1, r2), A22, q1, (d[4] / 2.0, c))
+    cvs.append(cv); its.append(it)
+    H0001, K11, cv, it = bls.solve_block(J, J1s, (r1, r2), A22, x.zerovector(), (0.0, 1.0))
+    cvs.append(cv); its.append(it)
+    # every cGL parameter enters F linearly: J2_11 = J2_12 = J2_22 = 0 exactly, so kappa3 (:270-271) is dropped
+    k = bt_nf_k2(prob, x, pv, i1, i2, p1, H0001)
+    f = -(k[0] + 2.0 * (k[1] * K11[0] + k[2] * K11[1]))
+    vals = [a, b, gamma, c, K10[0], K10[1], K11[0], K11[1], f * K10[0], f * K10[1]]
+    return dataclasses.replace(bt, nf=_bt_nf_dict(vals, (H2000, H1100, H0010, H0001)), converged=cvs, itlinear=its)
+
+
+def bogdanov_takens_normal_form_native(prob, bt: BogdanovTakens, ls: _GMRES, detailed=True) -> BogdanovTakens:
+    """The same as one library call (bk_bt_normal_form)."""
+    import dataclasses
+    ctx, x, pv = prob.ctx, bt.x0, bt.params
+    i1, i2 = bt.ipars
+    (q0, q1), (p0, p1) = bt.zeta, bt.zeta_star
+    H = [x.similar() for _ in range(4)] if detailed else [None] * 4
+    nf = (C.c_double * 10)()
+    cv, it = (C.c_int * 4)(), (C.c_int * 4)()
+    lo = ls._opts()
+    ctx.check(ctx.lib.bk_bt_normal_form(ctx.h, prob.h, _ptr(x.t), _carr(pv), len(pv), i1, i2, _ptr(q0.t), _ptr(q1.t), _ptr(p0.t),
+                                        _ptr(p1.t), 1 if detailed else 0, C.byref(lo), ls._pl(), *[_cptr(h) for h in H], nf, cv,
+                                        it), "bk_bt_normal_form")
+    if not detailed:
+        return dataclasses.replace(bt, nf=_bt_nf_dict(list(nf)), converged=[], itlinear=[])
+    return dataclasses.replace(bt, nf=_bt_nf_dict(list(nf), H), converged=[bool(c) for c in cv], itlinear=list(it))
+
+
+def _bt_from_branch(br, ind: int, prob, ls: _GMRES, ls_adj: _GMRES, tol, max_iterations, norm_inf, seed=0, detailed=True,
+                    native=True) -> BogdanovTakens:
+    """newton_bt_native from the "bt" point of a Hopf curve -> Jordan basis from the bordered vectors of the refined point ->
+    normal form there (the project's convention: the normal form is taken at the REFINED point)."""
+    if ls_adj is None:
+        raise TypeError('get_normal_form on a "bt" point needs ls_adj, the solver with the left preconditioner of the adjoint '
+                        "operator (bt_adjoint_solver)")
+    X = bt_point(br, ind)
+    with _lens2_at(prob, br.lens2, X.p[1]), _solver_state_kept(prob.ctx):
+        a, b = bt_start_vectors(prob, X, br.lens2, ls, ls_adj, seed=seed)
+        s = (newton_bt_native if native else newton_bt)(prob, X, br.lens2, a, b, ls, ls_adj, tol=tol, max_iterations=max_iterations,
+                                                         norm_inf=norm_inf)
+        if not s["converged"]:
+            raise RuntimeError(f"get_normal_form: newton_bt did not converge from the recorded point (residuals {s['residuals']})")
+        pv = _bt_pvec(prob, br.lens2, s["u"].p)
+        w1 = bt_terms(prob, s["u"].u, pv, a, b, ls, ls_adj, "w")["w1"]
+        bt = bt_jordan_basis(prob, s["u"], br.lens2, s["v1"], w1, ls, ls_adj)
+        f = bogdanov_takens_normal_form_native if native else bogdanov_takens_normal_form
+        bt = f(prob, bt, ls, detailed=detailed)
+    import dataclasses
+    return dataclasses.replace(bt, newton=s)
+
+
+def _bt_getx(a: float, s: float) -> float:
+    return -math.sqrt(abs(s) / a) if a > 0 else math.sqrt(abs(s) / abs(a))
+
+
+def bt_predictor(bt: BogdanovTakens, curve: str, ds: float):
+    """predictor(bt, Val(:HopfCurve), ds) (:342-400) and predictor(bt, Val(:FoldCurve), ds) (:408-434) evaluated at ds:
+    dict(pars = the predicted (p1, p2), omega (Hopf curve only), EigenVec, EigenVecAd, x0 = the predicted offset of the state).
+    On the Hopf curve the eigenvectors are (re, im) pairs: the eigenvector of [[0, 1], [2 x a, 0]] for +i omega (its adjoint's for
+    -i omega) in the basis (q0, q1) ((p0, p1)), formed with axpby calls."""
+    nf = bt.nf
+    if nf is None or "K10" not in nf:
+        raise ValueError("the predictor needs the detailed normal form (K10, K11, K2)")
+    a, b = nf["a"], nf["b"]
+    (q0, q1), (p0, p1) = bt.zeta, bt.zeta_star
+    xx = _bt_getx(a, ds)
+    if curve == "FoldCurve":
+        pars = bt.p + nf["K11"] * ds + nf["K2"] * (ds ** 2 / 2)
+        return dict(pars=pars, EigenVec=q0, EigenVecAd=p1, x0=q0.copy().scale_(xx))
+    if curve != "HopfCurve":
+        raise ValueError(f'predictor(bt, curve, ds): curve is "HopfCurve" or "FoldCurve" (got {curve!r}); the homoclinic predictor '
+                         "is not available")
+    beta1 = -abs(ds) if a > 0 else abs(ds)
+    beta2 = -b * xx
+    pars = bt.p + nf["K10"] * beta1 + nf["K11"] * beta2 + nf["K2"] * (beta2 ** 2 / 2)
+    A = np.array([[0.0, 1.0], [2 * xx * a, 0.0]])
+    vals, vecs = np.linalg.eig(A)
+    h = vecs[:, int(np.argmax(vals.imag))]
+    vals, vecs = np.linalg.eig(A.T)
+    ha = vecs[:, int(np.argmin(vals.imag))]
+    comb = lambda u0, u1, c: (u0.copy().scale_(c[0].real).add_(u1, c[1].real), u0.copy().scale_(c[0].imag).add_(u1, c[1].imag))
+    return dict(pars=pars, omega=math.sqrt(-2 * xx * a), EigenVec=comb(q0, q1, h), EigenVecAd=comb(p0, p1, ha),
+                x0=q0.copy().scale_(xx))
+
+
+def continuation_hopf_from_bt(bt: BogdanovTakens, prob, ls: _GMRES, cp: Cn.ContinuationPar, ds: float, newton_tol=None,
+                              max_iterations=15, bls=None, **kw):
+    """The Hopf curve restarted FROM the Bogdanov-Takens point: the Hopf-curve predictor at ``ds`` -> newton_hopf_native from
+    (x0 + predicted offset, p1, omega) with the predicted a = EigenVecAd, b = EigenVec at the predicted p2 -> continuation_hopf in
+    lens2 from the point it lands on.  Returns (branch, the newton_hopf_native result, the predictor)."""
+    lens1, lens2 = bt.lens
+    if prob.lens != lens1:
+        raise ValueError(f"the problem's lens is {prob.lens!r}, the first lens of the Bogdanov-Takens point is {lens1!r}")
+    pr = bt_predictor(bt, "HopfCurve", ds)
+    nrm = lambda z: _cscale(z, 1.0 / cnorm(z))
+    a, b = nrm(pr["EigenVecAd"]), nrm(pr["EigenVec"])
+    X0 = HopfVec(bt.x0.copy().add_(pr["x0"], 1.0), [pr["pars"][0], pr["omega"]])
+    tol = cp.newton_options.tol if newton_tol is None else newton_tol
+    with _lens2_at(prob, lens2, pr["pars"][1]):
+        s = newton_hopf_native(prob, X0, a, b, ls, tol=tol, max_iterations=max_iterations, bls=bls)
+        if not s["converged"]:
+            raise RuntimeError(f"continuation_hopf_from_bt: newton_hopf did not converge from the predictor (residuals {s['residuals']})")
+        a2, b2 = nrm(s["w"]), nrm(s["v"])
+        br = continuation_hopf(prob, s["u"], float(pr["pars"][1]), lens2, a2, b2, ls, cp, bls=bls, **kw)
+    return br, s, pr

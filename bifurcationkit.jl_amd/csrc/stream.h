@@ -1,5 +1,6 @@
 // Streaming scaffolding of the HBM-bound kernels: 256-thread workgroups, 16-byte loads per lane, the contiguous-burst grid-stride
-// walk and the wave64 sum (vecops.hip), and on top of them the two generic passes of fold.hip, hopf.hip, hopf_nf.hip, bautin.hip, nf1d.hip and nfnd.hip.
+// walk and the wave64 sum (vecops.hip), and on top of them the generic passes of fold.hip, hopf.hip, hopf_nf.hip, bautin.hip, nf1d.hip, nfnd.hip
+// and bt.hip: reducing, writing, and writing-and-reducing (stream_write_reduce, last in this file).
 //
 // How to add a streaming pass: write a plain struct with `static constexpr int NIN, U, FIELDS` (read streams; 16-byte items per
 // lane in flight; streams per vector: 2 when the stacked cGL fields p, p + n are walked side by side over n points, x[2 k + f] =
@@ -22,6 +23,7 @@ namespace bk {
 namespace {
 
 constexpr int kThreads = 256;
+constexpr int kVecPairs = -2;      // load path of stream_visit: pairs of elements in the order of the 16-byte path, 8-byte accesses
 
 inline int grid_for(size_t n, int per_thread, int max_blocks) {
     size_t b = (n + (size_t)kThreads * per_thread - 1) / ((size_t)kThreads * per_thread);
@@ -98,7 +100,9 @@ __device__ __forceinline__ void block_sum_store(const double (&s)[NV], double* p
 // HopfNfContract as eighteen pointers run out of SGPRs and are re-read from the kernel arguments inside the loop).  visit(integral_constant<int, K>, i, x) with x[K][NIN]:
 // K = 2 on the vector path (VEC == 2) -- x[0], x[1] are elements 2 i and 2 i + 1 of every stream; per iteration all NIN x UU
 // loads are issued before the first visit, items in the order q = 0..UU-1 -- and K = 1, element i, for the odd last element
-// (block 0 / thread 0, after the walk) and on the element-by-element path (VEC == 1).
+// (block 0 / thread 0, after the walk) and on the element-by-element path (VEC == 1).  VEC == kVecPairs walks the pairs of the
+// vector path in its order with two 8-byte loads per pair: for misaligned streams of a pass whose sums must not depend on the
+// alignment (stream_write_reduce).
 template <int U, int VEC, bool NTH, int F, int NB, class Visit>
 __device__ __forceinline__ void stream_visit(size_t n, const double* const (&in)[NB], Visit&& visit) {
     constexpr int NIN = NB * F;
@@ -109,14 +113,21 @@ __device__ __forceinline__ void stream_visit(size_t n, const double* const (&in)
         for (int j = 0; j < NIN; ++j) x[0][j] = stream(j)[i];
         visit(std::integral_constant<int, 1>{}, i, x);
     };
-    if (VEC == 2) {
+    if (VEC == 2 || VEC == kVecPairs) {
         stream_loop<U>(n >> 1, [&](auto uc, size_t i0, size_t st) {
             constexpr int UU = decltype(uc)::value;
             double2 v[UU][NIN];
 #pragma unroll
             for (int q = 0; q < UU; ++q)
 #pragma unroll
-                for (int j = 0; j < NIN; ++j) v[q][j] = ld2<NTH>(stream(j), i0 + q * st);
+                for (int j = 0; j < NIN; ++j) {
+                    if constexpr (VEC == 2) {
+                        v[q][j] = ld2<NTH>(stream(j), i0 + q * st);
+                    } else {
+                        const double* p = stream(j) + 2 * (i0 + q * st);
+                        v[q][j] = make_double2(p[0], p[1]);
+                    }
+                }
 #pragma unroll
             for (int q = 0; q < UU; ++q) {
                 double x[2][NIN];
@@ -241,6 +252,66 @@ int stream_write(bk_ctx* ctx, const char* name, size_t n, const Pass& pass) {
         stream_write_launch<decltype(V)::value, decltype(NT)::value>(ctx, pl.grid, n, pass, std::make_index_sequence<Pass::NIN / Pass::FIELDS>{});
     });
     BK_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ a pass that writes AND reduces
+// Pass: NIN, NOUT, NV, U, FIELDS, in[], out[], operator()(x, o, s) -- the element's outputs into o, its NV terms added to s.  The
+// outputs are stored as stream_write_kernel stores them, the terms summed as stream_reduce_kernel sums them.  Both load paths walk
+// pairs of elements in one order on one grid (VEC == 2: 16-byte accesses; kVecPairs when a stream is misaligned), so the sums are
+// bitwise the same run to run AND between aligned and misaligned operands; the element-by-element path of the two passes above
+// walks in another order, and their sums differ in the last bits between the paths.
+template <class Pass, int VEC, bool NTH, class... In>
+__global__ void __launch_bounds__(kThreads) stream_write_reduce_kernel(size_t n, Pass pass, double* __restrict__ partials,
+                                                                       In* __restrict__... in) {
+    constexpr int F = Pass::FIELDS;
+    const double* const ins[Pass::NIN / F] = {in...};
+    double s[Pass::NV];
+#pragma unroll
+    for (int k = 0; k < Pass::NV; ++k) s[k] = 0.0;
+    stream_visit<Pass::U, VEC, NTH, F>(n, ins, [&](auto kc, size_t i, const auto& x) {
+        constexpr int K = decltype(kc)::value;
+        double o[K][Pass::NOUT];
+#pragma unroll
+        for (int e = 0; e < K; ++e) pass(x[e], o[e], s);
+#pragma unroll
+        for (int j = 0; j < Pass::NOUT; ++j) {
+            double* out = pass.out[j / F] + (j % F) * n;
+            if constexpr (K == 2 && VEC == 2) {
+                st2(out, i, o[0][j], o[1][j]);
+            } else if constexpr (K == 2) {
+                out[2 * i] = o[0][j];
+                out[2 * i + 1] = o[1][j];
+            } else {
+                out[i] = o[0][j];
+            }
+        }
+    });
+    block_sum_store<Pass::NV>(s, partials);
+}
+
+template <int VEC, bool NTH, class Pass, size_t... J>
+void stream_write_reduce_launch(bk_ctx* ctx, int grid, size_t n, const Pass& pass, std::index_sequence<J...>) {
+    stream_write_reduce_kernel<Pass, VEC, NTH><<<dim3(grid), dim3(kThreads), 0, ctx->stream>>>(n, pass, ctx->d_partials, pass.in[J]...);
+}
+
+// sums[0..NV) all-reduced; the outputs must not alias the inputs or each other
+template <class Pass>
+int stream_write_reduce(bk_ctx* ctx, const char* name, size_t n, const Pass& pass, double* sums) {
+    static_assert(Pass::NV <= kPartialVals, "partial sums per workgroup");
+    const bool vec = all_aligned16(pass.in, n, Pass::FIELDS) && all_aligned16(pass.out, n, Pass::FIELDS);
+    const bool nth = vec && nt_hint(ctx, n * Pass::FIELDS);
+    const int grid = grid_for(n, 2 * Pass::U, kRedBlocks);          // the same on both load paths
+    {
+        ProfScope ps(ctx, name, 8.0 * n * (Pass::NIN + Pass::NOUT));
+        constexpr auto seq = std::make_index_sequence<Pass::NIN / Pass::FIELDS>{};
+        if (nth) stream_write_reduce_launch<2, true>(ctx, grid, n, pass, seq);
+        else if (vec) stream_write_reduce_launch<2, false>(ctx, grid, n, pass, seq);
+        else stream_write_reduce_launch<kVecPairs, false>(ctx, grid, n, pass, seq);
+        BK_HIP(ctx, hipGetLastError());
+    }
+    BK_TRY(reduce_finish(ctx, grid, Pass::NV, 0));
+    for (int k = 0; k < Pass::NV; ++k) sums[k] = ctx->h_red[k];
     return 0;
 }
 

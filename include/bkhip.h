@@ -1085,6 +1085,67 @@ int bk_potrap_monodromy_stats(bk_op* op, int* solves, int* failed, int* inner_it
 int bk_eig_krylovkit_lm(bk_ctx* ctx, bk_op* op, int nev, const bk_eig_opts* eopts, double* vals_re, double* vals_im,
                         double* vecs, double* vecs_im, size_t ldvecs, int* nvals, int* nconv, int* numops);
 
+/* ------------------------------------------------------------------ Bogdanov-Takens points ---------------
+ * The minimally augmented Bogdanov-Takens formulation (src/codim2/MinAugBT.jl), matrix-free, for BK_PDE_CGL2D on one rank (any
+ * other problem: the error of the Hopf entries).  Unknowns (x, p1, p2) for the two lenses ipar1 != ipar2,
+ *   G = (F, sigma1, sigma2),  [J a; b' 0][v1; sigma1] = [0; 1],  [J a; b' 0][v2; sigma2] = [v1; 0],
+ *                             [J' b; a' 0][w1; .] = [0; 1],      [J' b; a' 0][w2; .] = [w1; 0].
+ * J has a double zero eigenvalue at the point, so every solve is ONE GMRES on its bordered system with the left preconditioner
+ * diag(Pl, 1) (bk_bls_matrixfree_pl semantics): pl for J, pl_adj for J' (bk_precond_cgl_create with the sign of b flipped).   */
+/* One streaming pass over u and four real device vectors: row1 = s B(u)[v1, .]' w1, row2 = s (B(u)[v1, .]' w2 + B(u)[v2, .]' w1)
+ * (B = d2F, so <row, y> = s <w, d2F(u)[v, y]>), host sums[4] = s <w1, D_k v1> (sums[k]) and s (<w2, D_k v1> + <w1, D_k v2>)
+ * (sums[2 + k]) with D_k = dJ/dp for ipar1 (k = 0) and ipar2 (k = 1).  s = -1 with the bordered vectors: sigma1_x, sigma2_x and
+ * the row-major 2 x 2 block sigma_p.  row1, row2 must not alias an input or each other.  Deterministic.                      */
+int bk_bt_border(bk_problem* prob, const double* u, const double* params, int nparams, int ipar1, int ipar2, double s,
+                 const double* v1, const double* v2, const double* w1, const double* w2, double* row1, double* row2,
+                 double sums[4]);
+/* The bordered vectors at (x, params): (v1, v2, sigma[2]) when v1, v2 are given (pl required), (w1, w2) when w1, w2 are given
+ * (pl_adj required); each pair both or neither, at least one pair.  converged[4], itlinear[4] (each may be NULL): per solve in
+ * the order v1, v2, w1, w2 (1 and 0 for a pair that is not solved).                                                          */
+int bk_bt_terms(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, const double* a,
+                const double* b, const bk_gmres_opts* lsopts, bk_precond* pl, bk_precond* pl_adj, double* v1, double* v2,
+                double* w1, double* w2, double sigma[2], int converged[4], int itlinear[4]);
+/* btMALinearSolver (:118-228) with the bordered vectors of (x, params) given: [J dpF; sigma_x sigma_p][dX; dp] = [rhsu; rhsp]
+ * as ONE block-bordered solve with m = 2 (bk_bls_block_matrixfree_pl semantics): columns dF/dp1, dF/dp2 (analytic), rows and
+ * block from bk_bt_border with s = -1.  dX must be a fresh buffer.                                                           */
+int bk_bt_linsolve(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar1, int ipar2,
+                   const double* v1, const double* v2, const double* w1, const double* w2, const double* rhsu,
+                   const double rhsp[2], const bk_gmres_opts* lsopts, bk_precond* pl, double* dX, double dp[2], int* converged,
+                   int* itlinear);
+/* newton_bt under the semantics of _newton (src/Newton.jl:66-114), as bk_newton_hopf: (x, p[2]) = guess on entry, the
+ * Bogdanov-Takens point on exit; tol applies to BorderedArray(F, [sigma1, sigma2]) in the chosen norm; callback as bk_newton
+ * (p = p[0]).  Each point's v1, v2 are solved once and serve its residual and its Newton step; w1, w2 are solved per step.  On
+ * exit v1, v2 and sigma are those of the returned point, w1, w2 those of the last step taken.  itsolves[5] (may be NULL): GMRES
+ * iterations summed per solve, v1, v2, w1, w2 and the block solve; *unconverged (may be NULL): solves that returned unconverged. */
+int bk_newton_bt(bk_ctx* ctx, bk_problem* prob, double* x, double p[2], const double* params, int nparams, int ipar1, int ipar2,
+                 const double* a, const double* b, const bk_newton_opts* nopts, const bk_gmres_opts* lsopts, bk_precond* pl,
+                 bk_precond* pl_adj, double* v1, double* v2, double* w1, double* w2, double sigma[2], bk_newton_result* res,
+                 int itsolves[5], int* unconverged);
+
+/* The streaming passes of the Bogdanov-Takens normal form (src/codim2/NormalForms.jl:180-272) at (u, params) with the Jordan chains
+ * J q0 = 0, J q1 = q0, J' p1 = 0, J' p0 = p1, B = d2F:
+ *   bk_bt_nf_dots  host out[6] = <p1, B(q0, q0)>, <p0, B(q0, q0)>, <p1, B(q0, q1)>, <p0, B(q0, q1)>, <p1, B(q1, q1)>, <p0, B(q1, q1)>
+ *   bk_bt_nf_rhs   mode 0: out = k q1 - B(q0, q0) (H unused); mode 1: out = k q1 + H - B(q0, q1); out must not alias an input
+ *   bk_bt_nf_k2    host out[3] = <p1, B(H0001, H0001)>, <p1, D_1 H0001>, <p1, D_2 H0001>, D_k = dJ/dp for ipar1, ipar2
+ * One pass each, deterministic.                                                                                              */
+int bk_bt_nf_dots(bk_problem* prob, const double* u, const double* params, int nparams, const double* q0, const double* q1,
+                  const double* p0, const double* p1, double out[6]);
+int bk_bt_nf_rhs(bk_problem* prob, const double* u, const double* params, int nparams, int mode, double k, const double* q0,
+                 const double* q1, const double* H, double* out);
+int bk_bt_nf_k2(bk_problem* prob, const double* u, const double* params, int nparams, int ipar1, int ipar2, const double* p1,
+                const double* H0001, double out[3]);
+/* bogdanov_takens_normal_form (:141-335) through K2.  Host nf[10] = (a, b, gamma, c, K10[2], K11[2], K2[2]) with
+ *   a = <p1, B(q0, q0)> / 2,  b = <p0, B(q0, q0)> + <p1, B(q0, q1)>;   detailed = 0 returns after these (the rest NaN, no solve).
+ * detailed: H2000 and H1100 from two bordered solves [J p1; q0' 0] (Ainv, :205-213), H0010 / K10 and H0001 / K11 from two
+ * block-bordered solves with m = 2 of [J dpF; A12 A22] (:258-262; A12, A22 analytic from the bk_bt_border pass with s = +1), K2
+ * from bk_bt_nf_k2.  Every parameter of BK_PDE_CGL2D enters F linearly, so the second parameter derivatives of :234-246 vanish.
+ * converged[4], itlinear[4] (each may be NULL): per solve in the order H2000, H1100, (H0010, K10), (H0001, K11).  The
+ * coefficients of the homoclinic predictor (d, e, a1, b1 and their vectors) are not computed.                                */
+int bk_bt_normal_form(bk_ctx* ctx, bk_problem* prob, const double* x, const double* params, int nparams, int ipar1, int ipar2,
+                      const double* q0, const double* q1, const double* p0, const double* p1, int detailed,
+                      const bk_gmres_opts* lsopts, bk_precond* pl, double* H2000, double* H1100, double* H0010, double* H0001,
+                      double nf[10], int converged[4], int itlinear[4]);
+
 #ifdef __cplusplus
 }
 #endif
