@@ -1196,7 +1196,8 @@ def test_eigensolver_start_vector_and_thick_start(ctx):
     eig2 = hip.ShiftInvert(0.1, ls, tol=1e-9, maxiter=30, hermitian=True, save_vectors=False, x0=x0)
     vals2, _, ok2, nops2 = eig2(J, 6)
     # (no claim on the number of solves here: x0 lies in a 6-dimensional invariant subspace, the Arnoldi process breaks
-    # down to rounding after 6 steps and the rest of the basis is built on noise; the gain shows on a branch, (ii))
+    # down to rounding after 6 steps and the rest of the basis is built on noise; the gain shows on a branch, (ii).  What the
+    # solver returns from such a start and where the space runs out is pinned in tests/test_gpu_eig_exhaustion.py, groups A and B)
     assert ok2 and np.allclose(vals2.real, vals.real, rtol=0, atol=1e-8)
     dense = np.sort(np.linalg.eigvalsh(sh.J(s0["u"].numpy(), 0.1, 1.2).toarray()))[::-1][:6]
     assert np.allclose(np.sort(vals.real)[::-1], dense, rtol=0, atol=1e-8)
