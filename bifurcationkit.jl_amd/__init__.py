@@ -9,10 +9,11 @@ Only what the hot path needs:
   normal_form1d.py  normal form at simple branch points and folds of Swift-Hohenberg, predictors, automatic branch switching
   deflated_continuation.py  deflated continuation (DefCont): disconnected branches of Swift-Hohenberg by deflated Newton from noise
   periodic_orbit.py  periodic orbits of cGL by the trapezoid rule: functional, preconditioned Newton from the Hopf predictor, PALC
+  shooting.py  periodic orbits of cGL by standard shooting on a spectral ETDRK2 flow: flow, functional, Newton, PALC, Floquet multipliers
 
 Import name: ``bk_amd`` (the directory name is not a valid Python identifier; ``bk_amd.py`` at the repo
 root registers this package under that name).
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "hip", "continuation", "codim2", "normal_form1d", "deflated_continuation", "periodic_orbit"]
+__all__ = ["_lib", "hip", "continuation", "codim2", "normal_form1d", "deflated_continuation", "periodic_orbit", "shooting"]

@@ -305,6 +305,26 @@ SIGNATURES = {
     "bk_potrap_monodromy_solve": (I, [VP, VP, VP, c_int_p, c_int_p]),
     "bk_potrap_monodromy_stats": (I, [VP, c_int_p, c_int_p, c_int_p, c_int_p]),
     "bk_eig_krylovkit_lm": (I, [VP, VP, I, C.POINTER(EigOpts), c_double_p, c_double_p, VP, VP, SZ, c_int_p, c_int_p, c_int_p]),
+    "bk_flow_create": (I, [VP, I, C.POINTER(VP)]),
+    "bk_flow_destroy": (I, [VP]),
+    "bk_flow_evolve": (I, [VP, VP, D, I, c_double_p, I, VP]),
+    "bk_flow_jvp": (I, [VP, VP, VP, D, I, c_double_p, I, VP, VP]),
+    "bk_flow_coefficients": (I, [VP, D, c_double_p, c_double_p, c_double_p]),
+    "bk_flow_transform_paths": (I, [VP, c_int_p]),
+    "bk_flow_stats": (I, [VP, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "bk_shooting_create": (I, [VP, I, I, C.POINTER(VP)]),
+    "bk_shooting_destroy": (I, [VP]),
+    "bk_shooting_set_section": (I, [VP, VP, VP]),
+    "bk_shooting_get_section": (I, [VP, VP, VP]),
+    "bk_shooting_update_section": (I, [VP, VP, D, c_double_p, I]),
+    "bk_shooting_residual": (I, [VP, VP, D, c_double_p, I, VP, c_double_p]),
+    "bk_shooting_jvp": (I, [VP, VP, D, c_double_p, I, VP, D, VP, c_double_p]),
+    "bk_shooting_op_create": (I, [VP, VP, D, c_double_p, I, C.POINTER(VP)]),
+    "bk_shooting_op_apply": (I, [VP, VP, D, VP, c_double_p]),
+    "bk_shooting_op_stats": (I, [VP, c_int_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
+    "bk_shooting_transform_paths": (I, [VP, c_int_p]),
+    "bk_shooting_solve": (I, [VP, VP, VP, D, VP, c_double_p, C.POINTER(GmresOpts), C.POINTER(SolveResult)]),
+    "bk_shooting_monodromy_create": (I, [VP, VP, D, c_double_p, I, C.POINTER(VP)]),
 }
 
 _lib = None

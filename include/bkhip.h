@@ -1085,6 +1085,85 @@ int bk_potrap_monodromy_stats(bk_op* op, int* solves, int* failed, int* inner_it
 int bk_eig_krylovkit_lm(bk_ctx* ctx, bk_op* op, int nev, const bk_eig_opts* eopts, double* vals_re, double* vals_im,
                         double* vecs, double* vecs_im, size_t ldvecs, int* nvals, int* nconv, int* numops);
 
+/* ------------------------------------------------------------------ the spectral ETDRK2 flow of cGL (flow.hip) --------
+ * The flow that examples/cGL2d-shooting.jl builds from SplitODEProblem(Lap, NL) and ETDRK2 (:108-113, :123-128), for BK_PDE_CGL2D on
+ * one rank; any other problem kind gets the error of the Hopf entries.  Fixed-step Cox-Matthews ETDRK2, h = tau / nsteps, with the
+ * Dirichlet Laplacian exact in sine space (batched DST-I) and every pointwise term in N:
+ *     a^ = e^z u_n^ + h phi1(z) N^(u_n),   u_{n+1}^ = a^ + h phi2(z) (N^(a) - N^(u_n)),   z_k = h (lam_x[i] + lam_y[j]).
+ * Deviations from the example: its krylov = true approximates the phi functions and takes dt = 0.1; here they are exact per mode
+ * and the step count is the caller's.  B trajectories advance in lock-step; trajectory i is [u1; u2], N = 2 n doubles, at i N.  */
+typedef struct bk_flow bk_flow;
+int bk_flow_create(bk_problem* prob, int B, bk_flow** out);
+int bk_flow_destroy(bk_flow* flow);
+/* evolve(flow, x, par, tau).u (src/periodicorbit/Flow.jl) for B states: out = Phi(x, tau).  A step is four batched transforms, two
+ * pointwise passes and two spectral passes.  Errors: nsteps < 1, tau not finite, out aliasing x.                              */
+int bk_flow_evolve(bk_flow* flow, const double* x, double tau, int nsteps, const double* params, int nparams, double* out);
+/* jvp(flow, x, par, dx, tau) (Flow.jl): out = Phi(x, tau) and dout = dPhi(x, tau) dx from ONE march of state and tangent.  The
+ * tangent is the exact derivative of the discrete map where the example differences the flow (FiniteDifferencesMF, :127).
+ * Errors: as bk_flow_evolve; out aliasing x or dx; dout aliasing x, dx or out.                                                */
+int bk_flow_jvp(bk_flow* flow, const double* x, const double* dx, double tau, int nsteps, const double* params, int nparams,
+                double* out, double* dout);
+/* The three tables of a step h, n HOST doubles each in natural mode order: E = e^z, P1 = h phi1(z), P2 = h phi2(z).  phi2 is
+ * summed as a series for |z| < 1; z -> -inf gives E = 0 and finite P1, P2.  A diagnostic (the reference has no counterpart).   */
+int bk_flow_coefficients(bk_flow* flow, double h, double* E, double* P1, double* P2);
+/* Which kernel the transform passes of the last march dispatched to, per axis (x, y): as
+ * bk_precond_potrap_transform_paths.                                                                                          */
+int bk_flow_transform_paths(bk_flow* flow, int paths[2]);
+/* Counters since creation: marches that advanced the state, and the kernels the marches launched as the march itself adds them
+ * up (12 per step -- two per transform --, 2 for the first transform, the copies): a derived figure.  Either may be NULL.     */
+int bk_flow_stats(bk_flow* flow, long long* base_marches, long long* launches);
+
+/* ------------------------------------------------------------------ periodic orbits, standard shooting (shooting.hip) --------
+ * Shooting of src/periodicorbit/StandardShooting.jl (:138-257) with ds = 1 / M on the flow above and SectionSS of
+ * src/periodicorbit/Sections.jl:6-58, as examples/cGL2d-shooting.jl:123-150 uses them; BK_PDE_CGL2D on one rank.  Orbit vector: M
+ * states of N doubles on the device and the period T as ONE host scalar.  With next(i) = i + 1, next(M - 1) = 0:
+ *     G_i = Phi(x_i, T / M) - x_next(i),      G_T = (<x_0, normal> - <center, normal>) T            (Sections.jl:13).
+ * The M segments advance in lock-step (the reference's parallel = true); each takes nsteps steps of h = T / M / nsteps.       */
+typedef struct bk_shooting bk_shooting;
+/* Shooting(M, prob_sp, ETDRK2()) (:160-174; M = 1: simple shooting, :123-128).  Errors: more than one rank (asked first: a
+ * BK_PDE_CGL2D problem does not exist on several ranks), another problem kind, M < 1, nsteps < 1.                             */
+int bk_shooting_create(bk_problem* prob, int M, int nsteps, bk_shooting** out);
+int bk_shooting_destroy(bk_shooting* sh);
+/* SectionSS(normal, center): N doubles each, copied.                                                                          */
+int bk_shooting_set_section(bk_shooting* sh, const double* normal, const double* center);
+int bk_shooting_get_section(bk_shooting* sh, double* normal, double* center);
+/* updatesection! (:116-122): normal = F(x_0) / |F(x_0)|_2, center = x_0.                                                      */
+int bk_shooting_update_section(bk_shooting* sh, const double* x, double T, const double* params, int nparams);
+/* po_residual (:138-165): one march of the M segments, then the closure and the section dot in ONE pass (deterministic).  out
+ * must not alias x.                                                                                                           */
+int bk_shooting_residual(bk_shooting* sh, const double* x, double T, const double* params, int nparams, double* out, double* out_tail);
+/* po_jvp (:190-228): out_i = dPhi_i dx_i + F(Phi_i) (dT / M) - dx_next(i), *out_tail = (<x_0, normal> - <center, normal>) dT +
+ * <dx_0, normal> T (Sections.jl:43-45).  The period column is vector_field(flow, Phi_i) ds dT (:217), not the tau-derivative of
+ * the discrete map.  One march of state and tangent, then one pass.  out must not alias x or dx.                              */
+int bk_shooting_jvp(bk_shooting* sh, const double* x, double T, const double* params, int nparams, const double* dx, double dT,
+                    double* out, double* out_tail);
+/* dG(x, T) as an operator handle with one host tail scalar: REFERENCES x; the section in force is copied, so a later
+ * bk_shooting_set_section / update_section does not reach an existing operator.  Context option "shooting_store" (default 1): the
+ * base trajectory is marched once, here, u_n and the stage value a_n of every step are kept (2 nsteps M N doubles), and every
+ * application marches the tangent alone -- four transforms of 2 M fields per step instead of 4 M and no base nonlinearity.  0:
+ * state and tangent are marched together in every application.  Both give the same bits.  The record is one block that goes back
+ * to the handle sh when the operator is destroyed and is reused by the next operator (Newton creates one per step; only the first
+ * allocates), so sh must outlive its operators.  The budget: the workspace pool of the context has no limit of its own to take one
+ * from, so it is the option "shooting_store_max" (doubles, default 2^28); a record above it falls back to recomputation.      */
+int bk_shooting_op_create(bk_shooting* sh, const double* x, double T, const double* params, int nparams, bk_op** out);
+/* One application of an operator of bk_shooting_op_create: (out, *out_tail) = dG(x, T) (dx, dT), what bk_shooting_jvp returns,
+ * on the operator's route (stored or recomputed base).  out must not alias dx or the operator's x.                             */
+int bk_shooting_op_apply(bk_op* op, const double* dx, double dT, double* out, double* out_tail);
+/* For an operator of bk_shooting_op_create or bk_shooting_monodromy_create: whether it keeps the base trajectory, the base marches
+ * it has run and its applications, since creation.  Any pointer may be NULL.                                                  */
+int bk_shooting_op_stats(bk_op* op, int* stored, long long* base_marches, long long* applications);
+/* The transform kernels of the functional's last march, as bk_flow_transform_paths.                                           */
+int bk_shooting_transform_paths(bk_shooting* sh, int paths[2]);
+/* ONE unpreconditioned GMRES on dG [x; x_tail] = [rhs; rhs_tail] (the linear solve of newton(probSh, ...), cGL2d-shooting.jl
+ * :135-137): op from bk_shooting_op_create.  GMRES flavors only; x must not alias rhs.                                        */
+int bk_shooting_solve(bk_ctx* ctx, bk_op* op, const double* rhs, double rhs_tail, double* x, double* x_tail,
+                      const bk_gmres_opts* opts, bk_solve_result* result);
+/* dx -> MonodromyQaD_matrix_free(sh, x, par, dx) (src/periodicorbit/Floquet.jl:89-108) as an unbordered operator of length N:
+ * the M segment tangents applied in sequence on the base trajectory, which is marched and kept at creation (an error when it
+ * exceeds "shooting_store_max"); apply(x, a0, a1, out) = a0 x + a1 M x.  Copies what it needs of x; destroy with bk_op_destroy.
+ * The multipliers come from bk_eig_krylovkit_lm.                                                                              */
+int bk_shooting_monodromy_create(bk_shooting* sh, const double* x, double T, const double* params, int nparams, bk_op** out);
+
 /* ------------------------------------------------------------------ Bogdanov-Takens points ---------------
  * The minimally augmented Bogdanov-Takens formulation (src/codim2/MinAugBT.jl), matrix-free, for BK_PDE_CGL2D on one rank (any
  * other problem: the error of the Hopf entries).  Unknowns (x, p1, p2) for the two lenses ipar1 != ipar2,
